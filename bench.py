@@ -31,7 +31,13 @@ vs_baseline = value / reference updates/s (dense: 0.76 for 1 worker, 1.85 for
 the best 4-worker run); null for the configs the reference never
 ran.
 
-Usage: python bench.py [--gpus N] [--steps K] [--warmup W] [--model M]
+Usage: python bench.py [--gpus N] [--steps K] [--warmup W] [--model M] [--full] [--dump-outputs DIR]
+       A plain run sets up, warms up, times the K steps and prints one JSON line.
+       --full adds what takes a run of its own: with K < 2000 the untimed
+       continuation to 2000 rounds (accuracy_run).  --dump-outputs DIR writes the
+       last timed step's results (global model, worker deltas / losses, server
+       evaluation rows) as DIR/<name>.npy; inputs are seeded, so two builds run
+       with the same arguments can be compared array for array.
        N > 1: one rank per GPU over RCCL.  Under torch.distributed.run the
        ranks come from its environment; a plain ``python bench.py --gpus N``
        spawns the N ranks itself (before anything touches the GPU) and every
@@ -113,10 +119,19 @@ def parse(argv=None):
                     help="multi-GPU BSP: every rank hosts workers and a server replica, one RCCL all-reduce per "
                          "round (data-parallel variant)")
     ap.add_argument("--cpu", action="store_true", help="run on CPU (plumbing check only)")
+    ap.add_argument("--full", action="store_true",
+                    help="everything beyond the headline figure: with --steps < 2000 the untimed continuation to "
+                         "2000 rounds that reports the accuracy half of the metric (accuracy_run in the JSON; dense "
+                         "GPU runs only).  A plain run sets up, warms up, times the steps and prints the line")
     ap.add_argument("--no-accuracy-run", dest="accuracy_run", action="store_false",
-                    help="with --steps < 2000: skip the untimed continuation to 2000 rounds that reports the "
-                         "accuracy half of the metric (accuracy_run in the JSON; GPU runs only)")
+                    help="with --full: skip the untimed continuation to 2000 rounds")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last one left with its caller as DIR/<name>.npy: "
+                         "the global model (server_w), every worker's last delta and loss on rank 0, and the "
+                         "server's evaluation rows of the timed steps (a fixed seeded sample of arrays over 4M "
+                         "elements)")
     a = ap.parse_args(argv)
+    a.accuracy_run = a.accuracy_run and a.full
     m = MODELS[a.model]
     wide = a.model != "dense"
     for k in ("features", "train_rows", "test_rows", "consistency"):
@@ -365,6 +380,8 @@ def main(argv=None):
         res["native"]["phases_ms"] = dict(out["phases_ms"], drain=round((t0 + dt - t_run) * 1e3, 3))
     rows = list(eng.log.book.server)
     res.update(_accuracy_fields(rows, timed_from=n_warm, start_ms=eng.train_start_ms))
+    if a.dump_outputs:
+        res["dumped_outputs"] = _dump_outputs(a.dump_outputs, eng.server, eng.workers, rows, n_warm)
     if a.steps < ACC_ROUNDS and a.accuracy_run and a.model == "dense" and not a.cpu:
         eng.cfg.max_iters = ACC_ROUNDS - a.steps
         eng.run(close_log=False)
@@ -527,6 +544,8 @@ def bench_distributed(a):
             res["keyrange"] = dict(k, model_bytes_per_round=round(k["model_bytes"] / max(1, a.steps + a.warmup), 1),
                                    dense_vector_bytes=(a.features + 1) * 4)
         res.update(_accuracy_fields(list(book.server), timed_from=n_warm, start_ms=eng.train_start_ms))
+        if a.dump_outputs:  # (rank 0's view: the global model, its own workers, the server rows)
+            res["dumped_outputs"] = _dump_outputs(a.dump_outputs, eng.server, eng.workers, list(book.server), n_warm)
         if rccl is not None and rccl != world:
             raise SystemExit(f"bench.py: RCCL communicator has {rccl} ranks, world is {world}")
     if a.steps < ACC_ROUNDS and a.accuracy_run and a.model == "dense" and not async_mode and not a.cpu:
@@ -581,6 +600,46 @@ def _curve(server_rows, points=10):
     idx = sorted({int(i * (len(server_rows) - 1) / max(1, points - 1)) for i in range(points)})
     return [(round((server_rows[i][0] - ts0) / 1000.0, 6), round(server_rows[i][3], 4), round(server_rows[i][2], 4))
             for i in idx]
+
+
+DUMP_MAX_ELEMS = 1 << 22  # per array: 16 MB of float32 (3 large arrays at most: under the 64 MB a dump may take)
+
+
+def _dump_outputs(out_dir, server, workers, server_rows, timed_from):
+    """--dump-outputs: what the last timed step left with its caller, as
+    <out_dir>/<name>.npy -- server_w (the global model after the last update,
+    float32), worker_delta [workers, P] and worker_loss [workers] (every local
+    worker's last local solve, float32) and server_eval [timed rows, 2] (weighted
+    F1 and accuracy of the global model per timed step, float64; no timestamps).
+    An array over DUMP_MAX_ELEMS elements is sampled at fixed seeded positions
+    (they depend on its size alone, so two runs sample the same elements)."""
+    import numpy as np
+    import torch
+
+    def host(t):
+        t = t.detach().reshape(-1)
+        if t.numel() > DUMP_MAX_ELEMS:
+            idx = np.sort(np.random.default_rng(0).choice(t.numel(), DUMP_MAX_ELEMS, replace=False))
+            t = t[torch.from_numpy(idx).to(t.device)]
+        return np.ascontiguousarray(t.float().cpu().numpy(), dtype=np.float32)
+
+    os.makedirs(out_dir, exist_ok=True)
+    arrays = {}
+    if server is not None:
+        arrays["server_w"] = host(server.w)
+    deltas = [w.solver.delta for w in workers if getattr(w.solver, "delta", None) is not None]
+    if deltas and len(deltas) == len(workers):
+        flat = host(torch.cat([d.reshape(-1) for d in deltas]))
+        whole = flat.size == len(deltas) * deltas[0].numel()  # (a sampled array stays flat)
+        arrays["worker_delta"] = flat.reshape(len(deltas), -1) if whole else flat
+    if workers:
+        arrays["worker_loss"] = host(torch.cat([w.solver.loss.reshape(-1) for w in workers]))
+    rows = server_rows[timed_from:]
+    if rows:
+        arrays["server_eval"] = np.array([[r[2], r[3]] for r in rows], dtype=np.float64)
+    for name, x in arrays.items():
+        np.save(os.path.join(out_dir, name + ".npy"), x)
+    return sorted(arrays)
 
 
 def _fresh_log(eng):

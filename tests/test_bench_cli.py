@@ -84,6 +84,31 @@ def test_bench_single_gpu_default():
     assert d["time_to_f1_0.40_s"] is None or d["time_to_f1_0.40_s"] > 0
 
 
+def test_bench_dump_outputs_and_full(tmp_path):
+    """--dump-outputs writes the last timed step's results as .npy (float32 / float64),
+    identical from run to run (seeded inputs); --steps sets the timed rounds; --full is
+    accepted (its accuracy continuation is a GPU run's) and a plain run has none."""
+    import numpy as np
+
+    outs = []
+    for name, extra in (("a", []), ("b", ["--full"])):
+        d = tmp_path / name
+        p, lines = _run(SMALL + ["--workers", "2", "--dump-outputs", str(d)] + extra)
+        assert p.returncode == 0, p.stderr[-2000:]
+        res = json.loads(lines[0])
+        assert res["steps"] == 4 and res["timed_server_rows"] == 4 and res["ms_per_step"] > 0
+        assert "accuracy_run" not in res
+        assert res["dumped_outputs"] == ["server_eval", "server_w", "worker_delta", "worker_loss"]
+        outs.append({n: np.load(d / (n + ".npy")) for n in res["dumped_outputs"]})
+    a, b = outs
+    assert a["server_w"].dtype == np.float32 and a["server_w"].shape == (6 * 1024 + 6,)
+    assert a["worker_delta"].dtype == np.float32 and a["worker_delta"].shape == (2, 6 * 1024 + 6)
+    assert a["worker_loss"].shape == (2,) and a["server_eval"].dtype == np.float64 and a["server_eval"].shape == (4, 2)
+    assert np.isfinite(a["server_w"]).all() and np.abs(a["worker_delta"]).max() > 0
+    for n in a:
+        assert np.array_equal(a[n], b[n]), n
+
+
 @pytest.mark.parametrize("c", [2, -1])
 def test_bench_async_two_runs_same_engine(c):
     """Warm-up run then timed run of the same engine (SSP / ASP with a dedicated

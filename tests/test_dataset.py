@@ -9,12 +9,11 @@ import torch
 from psx._native import host
 from psx.utils import data
 
-MOCK = "/root/reference/mockData/sample_input_data.csv"
+# the reference project's mock data set (50 rows x 99 features + a binary label), stored as a fixture
+MOCK = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "sample_input_data.csv")
 
 
 def test_mock_csv_width_and_header_inference():
-    if not os.path.exists(MOCK):
-        pytest.skip("reference mock data not mounted")
     ds = data.load_csv(MOCK)
     assert ds.rows == 50 and ds.num_features == 99 and ds.Fp == 128
     assert set(ds.y.tolist()) <= {0, 1}

@@ -137,9 +137,7 @@ def test_ssp_worker_stops_early(c):
 
 
 def test_app_runners_as_processes(tmp_path):
-    mock = "/root/reference/mockData/sample_input_data.csv"
-    if not os.path.exists(mock):
-        pytest.skip("reference mock data not mounted")
+    mock = os.path.join(ROOT, "tests", "golden", "sample_input_data.csv")  # the reference's mock data set
     port = str(_free_port())
     env = dict(os.environ, PYTHONPATH=ROOT)
     srv = subprocess.Popen([sys.executable, "-m", "psx.apps.server_app_runner", "-training", mock, "-test", mock,

@@ -11,13 +11,13 @@ from psx.runtime.engine import LocalEngine
 from psx.utils.checkpoint import load_server, save_server
 from psx.utils.data import synth_binary, synth_finefood
 
-MOCK = "/root/reference/mockData/sample_input_data.csv"
+# the reference project's mock data set, stored as a fixture
+MOCK = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "sample_input_data.csv")
 
 
 def _mock_paths():
-    if os.path.exists(MOCK):
-        return MOCK, MOCK
-    pytest.skip("reference mock data not mounted")
+    assert os.path.exists(MOCK), MOCK
+    return MOCK, MOCK
 
 
 def test_config1_sequential_two_workers_mock(tmp_path):

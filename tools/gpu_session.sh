@@ -52,8 +52,8 @@ for s in $STEPS; do
       timeout -k 10 180 python -c "import __graft_entry__ as g; g.smoke()" > $OUT/smoke.log 2>&1
       rc=$?; echo "smoke rc=$rc"; tail -3 $OUT/smoke.log
       [ $rc -eq 0 ] || exit $rc ;;
-    bench)   # the driver's form, then the default
-      bench_run bench_short 300 --steps 20 --warmup 5 ${BENCH_ARGS:-} && bench_run bench 300 ${BENCH_ARGS:-} || exit 1 ;;
+    bench)   # the short form with its accuracy continuation, then the default
+      bench_run bench_short 300 --steps 20 --warmup 5 --full ${BENCH_ARGS:-} && bench_run bench 300 ${BENCH_ARGS:-} || exit 1 ;;
     ab)      # same-box A/B of round variants (3 repeats each by default)
       # AB_VARIANTS: space-separated env assignments, "-" = the defaults
       for v in ${AB_VARIANTS:-- PSX_LANES_LANE_EVAL=1 - PSX_LANES_LANE_EVAL=1}; do
@@ -94,7 +94,7 @@ for s in $STEPS; do
         [ -z "$n" ] && continue
         bench_run $n 300 $args; rc=$?; fatal_rc $rc && exit $rc
       done <<< "${SEC_RUNS:-w4 --workers 4 --steps 300 --warmup 30
-w4_short --workers 4 --steps 20 --warmup 5
+w4_short --workers 4 --steps 20 --warmup 5 --full
 w1 --workers 1 --steps 300 --warmup 30
 buf4096 --buffer 4096 --steps 100 --warmup 10
 long --steps 3000 --warmup 30}" ;;
