@@ -53,6 +53,17 @@ py::dict ctrl_dict(const Ctrl& c, int H) {
   (void)H;
   return d;
 }
+
+// ServerProtocol::run of either asynchronous server (GIL released): (code, worker, updates)
+template <class Server>
+py::tuple run_server(Server& s, int64_t checkpoint_every) {
+  AsyncStatus st;
+  {
+    py::gil_scoped_release nogil;
+    st = s.run(checkpoint_every);
+  }
+  return py::make_tuple(st.code, st.worker, st.updates);
+}
 }  // namespace
 
 PYBIND11_MODULE(_psx_hip, m) {
@@ -696,17 +707,7 @@ PYBIND11_MODULE(_psx_hip, m) {
            }),
            py::arg("cfg"))
       .def("begin", &PeerServer::begin, py::call_guard<py::gil_scoped_release>())
-      .def(
-          "run",
-          [](PeerServer& s, int64_t checkpoint_every) {
-            AsyncStatus st;
-            {
-              py::gil_scoped_release nogil;
-              st = s.run(checkpoint_every);
-            }
-            return py::make_tuple(st.code, st.worker, st.updates);
-          },
-          py::arg("checkpoint_every") = 0)
+      .def("run", &run_server<PeerServer>, py::arg("checkpoint_every") = 0)
       .def("run_bsp", &PeerServer::run_bsp, py::arg("rounds"), py::arg("r0"), py::call_guard<py::gil_scoped_release>())
       .def("run_bsp_async", &PeerServer::run_bsp_async, py::arg("rounds"), py::arg("r0"))
       .def("run_bsp_join", &PeerServer::run_bsp_join, py::call_guard<py::gil_scoped_release>())
@@ -783,17 +784,7 @@ PYBIND11_MODULE(_psx_hip, m) {
            }),
            py::arg("p2p"), py::arg("cfg"), py::arg("stream"), py::keep_alive<1, 2>())
       .def("begin", &AsyncServer::begin)
-      .def(
-          "run",
-          [](AsyncServer& s, int64_t checkpoint_every) {
-            AsyncStatus st;
-            {
-              py::gil_scoped_release nogil;
-              st = s.run(checkpoint_every);
-            }
-            return py::make_tuple(st.code, st.worker, st.updates);
-          },
-          py::arg("checkpoint_every") = 0)
+      .def("run", &run_server<AsyncServer>, py::arg("checkpoint_every") = 0)
       .def("fail", &AsyncServer::fail)
       .def("set_stream", [](AsyncServer& s, uintptr_t st) { s.set_stream(S(st)); })
       .def_property("updates", &AsyncServer::updates, &AsyncServer::set_updates)

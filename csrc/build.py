@@ -130,7 +130,7 @@ def build_hip(force=False, jobs=8):
     headers = sorted(glob.glob(os.path.join(CSRC, "kernels", "*.h")) + glob.glob(os.path.join(CSRC, "solver", "*.h")) +
                      glob.glob(os.path.join(CSRC, "comm", "*.h")) + glob.glob(os.path.join(CSRC, "runtime", "*.h")) +
                      [os.path.join(CSRC, "host", "capi.h"), os.path.join(CSRC, "host", "ctrl.h"),
-                     os.path.join(CSRC, "host", "sink_record.h")])
+                     os.path.join(CSRC, "host", "sink_record.h"), os.path.join(CSRC, "host", "server_protocol.h")])
     out = os.path.join(PKG, "_psx_hip" + _ext_suffix())
     cflags = [
         "-O3",

@@ -17,6 +17,9 @@
 //     tokens; the device runs the enqueued schedule behind it.
 // The tracker, token queue and metrics sink belong to the host runtime
 // (_psx_host) and are driven through its C ABI (csrc/host/capi.h).
+// The protocol itself (bootstrap, token loop, watchdog, retirement, checkpoint
+// stop) is ServerProtocol (csrc/host/server_protocol.h), shared with PeerServer;
+// this class is its point-to-point data plane.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -29,6 +32,7 @@
 
 #include "../comm/rccl_comm.h"
 #include "../host/capi.h"
+#include "../host/server_protocol.h"
 
 namespace psx {
 
@@ -178,68 +182,33 @@ struct AsyncServerCfg {
   int cpu = 0;
 };
 
-enum AsyncCode : int {
-  kAsyncDone = 0,        // every worker sent its final delta (or failed)
-  kAsyncErrorToken = 1,  // `worker` reported an error: caller decides (retire via fail(), or abort)
-  kAsyncWatchdog = 2,    // `worker` busy and silent longer than the timeout
-  kAsyncCheckpoint = 3,  // `updates` reached a multiple of checkpoint_every
-};
-
-struct AsyncStatus {
-  int code = kAsyncDone;
-  int worker = -1;
-  int64_t updates = 0;
-};
-
-class AsyncServer {
+class AsyncServer : public ServerProtocol {
  public:
   AsyncServer(P2P* p2p, const AsyncServerCfg& cfg, hipStream_t stream);
-  // New run: workers that finished the previous run rejoin (failed ones stay
-  // retired), every live worker gets the weights of its current clock (the
-  // bootstrap: vc 0 on a fresh tracker).
-  void begin();
-  // Serve tokens until every worker finished (or a code that needs the caller).
-  AsyncStatus run(int64_t checkpoint_every);
-  // Retire worker k (failed): the tracker stops waiting for it; the workers it
-  // held back are answered.
-  void fail(int k);
-  int64_t updates() const { return updates_; }
-  void set_updates(int64_t u) { updates_ = u; }
-  int64_t tokens() const { return tokens_; }
-  double host_us_per_update() const { return updates_run_ ? host_ns_ / 1000.0 / (double)updates_run_ : 0.0; }
-  std::vector<int> failed() const;
   void set_stream(hipStream_t s) { stream_ = s; }
+  int64_t sparse_pulls() const { return sparse_pulls_; }
+  int64_t dense_pulls() const { return dense_pulls_; }
+  int64_t pull_floats() const { return pull_floats_; }  // values + ids moved by pulls
+
+ protected:
+  void start(bool new_run) override;
+  // receive + update + (log worker) evaluation of the token's delta
+  void apply(const CtrlToken& t) override;
+  // the weights to every released worker, one group
+  void release(int k, int64_t vc, const int* ks, const int64_t* vs, int n) override;
 
  private:
-  const HostApi& api() const { return *api_; }
-  void check_api(int rc, const char* what) const;
-  void send_weights(const int* ks, const int64_t* vs, int n);
-  void apply_and_log(const CtrlToken& t);
   void apply_cpu(const CtrlToken& t);
   void eval_cpu(char* slot, uint64_t seq);
-  int log_worker() const;
   int peer_of(int k) const { return cfg_.peer.empty() ? k + 1 : cfg_.peer[k]; }
 
   P2P* comm_;
   AsyncServerCfg cfg_;
   hipStream_t stream_;
-  const HostApi* api_;
-  std::vector<uint8_t> finished_, failed_;  // this run
-  std::vector<uint8_t> dead_;               // failed in any run: never revived
-  std::vector<double> busy_since_;  // < 0: not busy (weights not sent / delta back)
-  std::vector<int> rel_k_;
-  std::vector<int64_t> rel_v_;
   int64_t log_pos_ = 0;                 // ids appended to the log so far
   std::vector<int64_t> last_pos_;       // log position of each worker's last pull (-1: dense next)
   std::vector<int> since_dense_;        // sparse pulls since the worker's last dense pull
   int64_t sparse_pulls_ = 0, dense_pulls_ = 0, pull_floats_ = 0;
-
- public:
-  int64_t sparse_pulls() const { return sparse_pulls_; }
-  int64_t dense_pulls() const { return dense_pulls_; }
-  int64_t pull_floats() const { return pull_floats_; }  // values + ids moved by pulls
-  int64_t updates_ = 0, tokens_ = 0, updates_run_ = 0;
-  double host_ns_ = 0.0;
 };
 
 // In-process stand-ins for the worker ranks of a LocalP2P server: thread k

@@ -28,7 +28,6 @@ int64_t epoch_ms() {
   return std::chrono::duration_cast<std::chrono::milliseconds>(std::chrono::system_clock::now().time_since_epoch())
       .count();
 }
-constexpr int kKindDelta = 0, kKindFinal = 1, kKindError = 2;
 
 }  // namespace
 
@@ -324,7 +323,7 @@ void LocalFeeder::run(int k) {
 }
 
 AsyncServer::AsyncServer(P2P* comm, const AsyncServerCfg& cfg, hipStream_t stream)
-    : comm_(comm), cfg_(cfg), stream_(stream) {
+    : ServerProtocol("AsyncServer"), comm_(comm), cfg_(cfg), stream_(stream) {
   if (!comm_) throw std::invalid_argument("AsyncServer: null transport");
   // one rank per worker, or (peer map) several workers per worker rank: every
   // worker's rank in [1, size)
@@ -333,8 +332,7 @@ AsyncServer::AsyncServer(P2P* comm, const AsyncServerCfg& cfg, hipStream_t strea
   for (int p : cfg.peer)
     if (p < 1 || p >= comm_->size()) throw std::invalid_argument("AsyncServer: a worker's peer rank is outside the communicator");
   if (!cfg.api || !cfg.tracker || !cfg.ctrl) throw std::invalid_argument("AsyncServer: missing host runtime handles");
-  api_ = reinterpret_cast<const HostApi*>(cfg.api);
-  if (api_->version != kHostApiVersion) throw std::runtime_error("AsyncServer: host runtime C ABI version mismatch");
+  bind(cfg.api, cfg.tracker, cfg.ctrl, cfg.nworkers, cfg.worker_timeout_s);
   if (!cfg.w || cfg.P <= 0) throw std::invalid_argument("AsyncServer: no weights");
   if (cfg.model == kAsyncWideSparse) {
     if (!cfg.ubuf || !cfg.dbuf || cfg.KP < 1 || cfg.umax < 0) throw std::invalid_argument("AsyncServer: sparse buffers");
@@ -348,9 +346,6 @@ AsyncServer::AsyncServer(P2P* comm, const AsyncServerCfg& cfg, hipStream_t strea
     throw std::invalid_argument("AsyncServer: one peer per worker");
   if (!cfg.replies.empty() && (int)cfg.replies.size() != cfg.nworkers)
     throw std::invalid_argument("AsyncServer: one reply queue per worker");
-  finished_.assign(cfg.nworkers, 0);
-  failed_.assign(cfg.nworkers, 0);
-  dead_.assign(cfg.nworkers, 0);
   last_pos_.assign(cfg.nworkers, -1);
   since_dense_.assign(cfg.nworkers, 0);
   if (cfg.sparse_pull) {
@@ -358,41 +353,18 @@ AsyncServer::AsyncServer(P2P* comm, const AsyncServerCfg& cfg, hipStream_t strea
     if (!cfg.lids || !cfg.lvals || cfg.logcap < 1 || (int)cfg.replies.size() != cfg.nworkers)
       throw std::invalid_argument("AsyncServer: sparse pull needs the ring log and one reply queue per worker");
   }
-  busy_since_.assign(cfg.nworkers, -1.0);
-  rel_k_.resize(cfg.nworkers + 1);
-  rel_v_.resize(cfg.nworkers + 1);
 }
 
-void AsyncServer::check_api(int rc, const char* what) const {
-  if (rc < 0) throw std::runtime_error(std::string("AsyncServer: ") + what + ": " + api_->last_error());
+void AsyncServer::start(bool new_run) {
+  if (new_run) std::fill(last_pos_.begin(), last_pos_.end(), -1);  // every run starts with a dense pull
 }
 
-int AsyncServer::log_worker() const {
-  // server rows follow the deltas of worker 0 (ServerProcessor.java:154-165), or of
-  // the lowest surviving worker once 0 has failed
-  for (int j = 0; j < cfg_.nworkers; ++j)
-    if (!failed_[j]) return j;
-  return -1;
-}
-
-std::vector<int> AsyncServer::failed() const {
-  std::vector<int> out;
-  for (int j = 0; j < cfg_.nworkers; ++j)
-    if (failed_[j]) out.push_back(j);
-  return out;
-}
-
-void AsyncServer::send_weights(const int* ks, const int64_t* vs, int n) {
-  bool any = false;
-  for (int i = 0; i < n; ++i) any |= !finished_[ks[i]];
-  if (!any) return;
-  const double t = now_s();
+void AsyncServer::release(int, int64_t, const int* ks, const int64_t* vs, int n) {
+  if (n == 0) return;
   const int KP = cfg_.KP;
   comm_->group_start();
   for (int i = 0; i < n; ++i) {
     const int j = ks[i];
-    if (finished_[j]) continue;
-    busy_since_[j] = t;
     if (!cfg_.sparse_pull) {
       if (!cfg_.replies.empty()) {  // several workers per rank: which one the weights are for
         CtrlToken r{};
@@ -443,32 +415,6 @@ void AsyncServer::send_weights(const int* ks, const int64_t* vs, int n) {
     last_pos_[j] = log_pos_;
   }
   comm_->group_end();
-}
-
-void AsyncServer::begin() {
-  std::fill(last_pos_.begin(), last_pos_.end(), -1);  // every run starts with a dense pull
-  std::fill(finished_.begin(), finished_.end(), 0);
-  std::fill(failed_.begin(), failed_.end(), 0);
-  std::fill(busy_since_.begin(), busy_since_.end(), -1.0);
-  int n = 0;
-  for (int j = 0; j < cfg_.nworkers; ++j) {
-    int live = api().tracker_is_live((void*)cfg_.tracker, j);
-    check_api(live, "tracker is_live");
-    if (!live && !dead_[j]) {  // retired because it finished the previous run: rejoins
-      check_api(api().tracker_revive((void*)cfg_.tracker, j), "tracker revive");
-      live = 1;
-    }
-    if (!live) {  // failed in an earlier run (or retired in a resumed checkpoint)
-      failed_[j] = finished_[j] = dead_[j] = 1;
-      continue;
-    }
-    const int64_t u = api().tracker_clock((void*)cfg_.tracker, j);
-    if (u > 0) api().tracker_sent((void*)cfg_.tracker, j, u);  // a later run resumes at the tracked clocks
-    rel_k_[n] = j;
-    rel_v_[n] = u;
-    ++n;
-  }
-  send_weights(rel_k_.data(), rel_v_.data(), n);  // the bootstrap (ServerProcessor.java:75-87)
 }
 
 // Host-memory update (CPU ranks): the same arithmetic as the update kernels
@@ -568,14 +514,12 @@ void AsyncServer::eval_cpu(char* slot, uint64_t seq) {
   __atomic_store_n(reinterpret_cast<uint64_t*>(slot + 1032), (uint64_t)seq, __ATOMIC_RELEASE);
 }
 
-void AsyncServer::apply_and_log(const CtrlToken& t) {
+void AsyncServer::apply(const CtrlToken& t) {
   const int k = t.worker;
   const int peer = peer_of(k);
   const int64_t v = t.vc;
   if (cfg_.cpu) {
     apply_cpu(t);
-    ++updates_;
-    ++updates_run_;
     if (cfg_.sink && k == log_worker()) {
       uint64_t seq = 0;
       uintptr_t addr = 0;
@@ -607,8 +551,6 @@ void AsyncServer::apply_and_log(const CtrlToken& t) {
     else
       launch_axpy(cfg_.w, cfg_.buf, cfg_.lr, cfg_.P, stream_);
   }
-  ++updates_;
-  ++updates_run_;
   if (cfg_.sink && k == log_worker()) {  // the global model's test metrics, one server row
     uint64_t seq = 0;
     uintptr_t addr = 0;
@@ -624,73 +566,6 @@ void AsyncServer::apply_and_log(const CtrlToken& t) {
   }
   const hipError_t e = hipGetLastError();
   if (e != hipSuccess) throw std::runtime_error(std::string("AsyncServer launch: ") + hipGetErrorString(e));
-}
-
-void AsyncServer::fail(int k) {
-  if (k < 0 || k >= cfg_.nworkers) throw std::out_of_range("AsyncServer::fail: worker id");
-  failed_[k] = finished_[k] = dead_[k] = 1;
-  busy_since_[k] = -1.0;
-  const int n = api().tracker_retire((void*)cfg_.tracker, k, rel_k_.data(), rel_v_.data(), (int)rel_k_.size());
-  check_api(n, "tracker retire");
-  send_weights(rel_k_.data(), rel_v_.data(), n);
-}
-
-AsyncStatus AsyncServer::run(int64_t checkpoint_every) {
-  AsyncStatus st;
-  const double poll = cfg_.worker_timeout_s < 1.0 ? cfg_.worker_timeout_s : 1.0;
-  for (;;) {
-    int open = 0;
-    for (int j = 0; j < cfg_.nworkers; ++j) open += !finished_[j];
-    if (open == 0) break;
-    CtrlToken t;
-    const int got = api().ctrl_pop((void*)cfg_.ctrl, &t, poll);
-    check_api(got, "token pop");
-    if (!got) {  // watchdog: a worker holding weights that stays silent has failed
-      const double now = now_s();
-      for (int j = 0; j < cfg_.nworkers; ++j)
-        if (!finished_[j] && busy_since_[j] >= 0.0 && now - busy_since_[j] > cfg_.worker_timeout_s) {
-          st.code = kAsyncWatchdog;
-          st.worker = j;
-          st.updates = updates_;
-          return st;
-        }
-      continue;
-    }
-    const auto h0 = std::chrono::steady_clock::now();
-    ++tokens_;
-    const int k = t.worker;
-    if (k < 0 || k >= cfg_.nworkers) throw std::runtime_error("AsyncServer: token from an unknown worker");
-    if (t.kind == kKindError) {
-      st.code = kAsyncErrorToken;
-      st.worker = k;
-      st.updates = updates_;
-      return st;
-    }
-    if (finished_[k]) throw std::runtime_error("AsyncServer: delta from a finished worker " + std::to_string(k));
-    busy_since_[k] = -1.0;
-    apply_and_log(t);
-    int n = api().tracker_on_delta((void*)cfg_.tracker, k, t.vc, rel_k_.data(), rel_v_.data(), (int)rel_k_.size());
-    check_api(n, "tracker on_delta");
-    if (t.kind == kKindFinal) {
-      // a finished worker no longer holds the others back (its frozen clock would
-      // stall an SSP worker D ahead forever)
-      finished_[k] = 1;
-      const int m = api().tracker_retire((void*)cfg_.tracker, k, rel_k_.data() + n, rel_v_.data() + n,
-                                         (int)rel_k_.size() - n);
-      check_api(m, "tracker retire");
-      n += m;
-    }
-    send_weights(rel_k_.data(), rel_v_.data(), n);
-    host_ns_ += std::chrono::duration<double, std::nano>(std::chrono::steady_clock::now() - h0).count();
-    if (checkpoint_every > 0 && updates_ % checkpoint_every == 0) {
-      st.code = kAsyncCheckpoint;
-      st.updates = updates_;
-      return st;
-    }
-  }
-  st.code = kAsyncDone;
-  st.updates = updates_;
-  return st;
 }
 
 }  // namespace psx

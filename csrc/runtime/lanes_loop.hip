@@ -1477,6 +1477,17 @@ int64_t LanesLoop::run_async(int64_t updates, hipStream_t stream, double max_wai
   bool stopping = updates <= 0;
   std::vector<int> ks((size_t)cfg_.N);
   std::vector<int64_t> vs((size_t)cfg_.N);
+  // the first n entries of the tracker's release list (ks, vs): those workers' lanes want
+  // the weights of that clock
+  auto want_released = [&](int n) {
+    for (int i = 0; i < n; ++i) {
+      const int j = ks[i] >= 0 && ks[i] < cfg_.N ? lane_of_[ks[i]] : -1;
+      if (j < 0) throw std::logic_error("LanesLoop: the tracker released a worker this loop does not host");
+      if (state_[j] == kGone) continue;
+      state_[j] = kWant;
+      want_vc_[j] = vs[i];
+    }
+  };
   // a lane whose worker crashed / left: it gets its stop record now (its workgroups
   // leave the launch), the tracker retires the worker (the others are no longer held
   // back by its clock) and the lanes that releases are dispatched
@@ -1498,13 +1509,7 @@ int64_t LanesLoop::run_async(int64_t updates, hipStream_t stream, double max_wai
     }
     const int n = api().tracker_retire(trk, k, ks.data(), vs.data(), cfg_.N);
     check(n, "tracker retire");
-    for (int i = 0; i < n; ++i) {
-      const int j = ks[i] >= 0 && ks[i] < cfg_.N ? lane_of_[ks[i]] : -1;
-      if (j < 0) throw std::logic_error("LanesLoop: the tracker released a worker this loop does not host");
-      if (state_[j] == kGone) continue;
-      state_[j] = kWant;
-      want_vc_[j] = vs[i];
-    }
+    want_released(n);
   };
   try {
     auto start_ready = [&](double now) {
@@ -1557,13 +1562,7 @@ int64_t LanesLoop::run_async(int64_t updates, hipStream_t stream, double max_wai
         state_[l] = kIdle;
         const int n = api().tracker_on_delta(trk, cfg_.k[l], vc, ks.data(), vs.data(), cfg_.N);
         check(n, "tracker");
-        for (int i = 0; i < n; ++i) {
-          const int j = ks[i] >= 0 && ks[i] < cfg_.N ? lane_of_[ks[i]] : -1;
-          if (j < 0) throw std::logic_error("LanesLoop: the tracker released a worker this loop does not host");
-          if (state_[j] == kGone) continue;
-          state_[j] = kWant;
-          want_vc_[j] = vs[i];
-        }
+        want_released(n);
         if (!stop.empty() && stop[l] >= 0 && lane_started[l] >= stop[l]) lane_leave(l, false);
         if (deadline_ms > 0.0 && epoch_ms() >= deadline_ms) stopping = true;
         start_ready(epoch_ms() - cfg_.t0_ms);

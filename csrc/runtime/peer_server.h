@@ -15,6 +15,10 @@
 //     64-B command per token into a pinned ring, and answers each release on
 //     the worker's rank reply queue with its pull tag.  It never waits for the
 //     device and never synchronises a stream per delta (host_us_per_update).
+// The protocol itself (bootstrap, token loop, watchdog, retirement, checkpoint
+// stop: begin / run / fail) is ServerProtocol (csrc/host/server_protocol.h),
+// shared with AsyncServer; this class is its data plane -- the commands, their
+// batching, the rings and the persistent launch -- and the BSP rounds (run_bsp).
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -27,6 +31,7 @@
 
 #include "../comm/peer_bus.h"
 #include "../host/capi.h"
+#include "../host/server_protocol.h"
 #include "../kernels/server_persist.h"
 #include "async_server.h"
 
@@ -70,19 +75,14 @@ struct PeerServerCfg {
   int ahead = 0;
 };
 
-class PeerServer {
+class PeerServer : public ServerProtocol {
  public:
   PeerServer(const PeerServerCfg& cfg, hipStream_t stream);
   ~PeerServer();
   PeerServer(const PeerServer&) = delete;
   PeerServer& operator=(const PeerServer&) = delete;
-  // New run (AsyncServer::begin semantics): launches the persistent kernel if it is
-  // not running and sends every live worker the weights of its clock.
-  void begin();
-  // Serve tokens until every worker finished (the launch then drains: w is final),
-  // a checkpoint is due (drained as well) or a worker needs the caller's decision.
-  AsyncStatus run(int64_t checkpoint_every);
-  void fail(int k);
+  // begin() / run() / fail() (ServerProtocol) launch the persistent kernel if it is not
+  // running; run() returns done or a checkpoint with the launch drained (w is final).
   // peer_sum BSP: `rounds` rounds from round r0 -- one command per round (the ranks' sums
   // summed, applied, the weights written into every rank's receive slot; the server row of
   // the global model into the metrics sink, vc = the round), the tracker advanced per
@@ -120,35 +120,37 @@ class PeerServer {
     launch();
     stop();
   }
-  int64_t updates() const { return updates_; }
-  void set_updates(int64_t u) { updates_ = u; }
-  int64_t tokens() const { return tokens_; }
   int64_t commands() const { return (int64_t)cmds_; }
-  double host_us_per_update() const { return updates_run_ ? host_ns_ / 1000.0 / (double)updates_run_ : 0.0; }
-  std::vector<int> failed() const;
   bool running() const { return running_; }
   // (worker, vc) of every delta in arrival order (the single partition's order; tests
   // replay it through a fresh tracker), the first kMaxArrivals
   static constexpr size_t kMaxArrivals = 1 << 20;
   const std::vector<std::pair<int, int64_t>>& arrivals() const { return arrivals_; }
 
+ protected:
+  void start(bool) override { launch(); }
+  void end() override { stop(); }
+  // (the delta is in the inbox already: the command of release() applies it)
+  void apply(const CtrlToken& t) override {
+    if (arrivals_.size() < kMaxArrivals) arrivals_.emplace_back(t.worker, t.vc);
+  }
+  // command k (-1: none) + releases (ks, vs) + replies; returns after the host part.
+  // A delta (k >= 0) joins the open batch (flushed by flush_batch, at a logging delta or
+  // when full); a release-only command flushes the batch first
+  void release(int k, int64_t vc, const int* ks, const int64_t* vs, int n) override;
+  bool pending() const override { return !bat_.empty(); }
+  void flush() override { flush_batch(); }
+  void check_plane() override { check_device(); }
+
  private:
-  const HostApi& api() const { return *api_; }
-  void check_api(int rc, const char* what) const;
   void check_device() const;
   void launch();
   void wait_ring();  // until the next command's ring slot is free
   void write_cmd(const SrvCmd& c);
-  // command k (-1: none) + releases (ks, vs) + replies; returns after the host part.
-  // A delta (k >= 0) joins the open batch (flushed by flush_batch, at a logging delta or
-  // when full); a release-only command flushes the batch first
-  void issue(int k, int64_t vc, const int* ks, const int64_t* vs, int n);
   void flush_batch();
-  int log_worker() const;
 
   PeerServerCfg cfg_;
   hipStream_t stream_;
-  const HostApi* api_;
   int NS_ = 0;
   // device workspace
   void* ws_ = nullptr;
@@ -163,10 +165,6 @@ class PeerServer {
   int64_t launches_ = 0;
   bool running_ = false;
   std::vector<uint32_t> ptag_;  // pulls sent per worker (the device counters' mirror)
-  std::vector<uint8_t> finished_, failed_, dead_;
-  std::vector<double> busy_since_;
-  std::vector<int> rel_k_;
-  std::vector<int64_t> rel_v_;
   std::vector<std::pair<int, int64_t>> arrivals_;
   // the open batch: entries, its server-row slot (the last entry's), the replies owed
   TagChunk* ent_ring_ = nullptr;  // pinned [ent_cap_][kEntChunks]
@@ -179,8 +177,6 @@ class PeerServer {
   int64_t bat_vc_ = 0;
   std::vector<CtrlToken> bat_rep_;
   int64_t batches_ = 0, batched_deltas_ = 0;
-  int64_t updates_ = 0, tokens_ = 0, updates_run_ = 0;
-  double host_ns_ = 0.0;
   uint64_t bsp_n_ = 0;  // BSP rounds commanded so far (the tag of the last one)
   long long* tr_ = nullptr;
   int tr_cap_ = 0;

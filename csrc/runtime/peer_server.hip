@@ -17,21 +17,17 @@
 
 namespace psx {
 namespace {
-double now_s() {
-  return std::chrono::duration<double>(std::chrono::steady_clock::now().time_since_epoch()).count();
-}
 size_t align_up(size_t v, size_t a) { return (v + a - 1) / a * a; }
-constexpr int kKindDelta = 0, kKindFinal = 1, kKindError = 2;
 }  // namespace
 
-PeerServer::PeerServer(const PeerServerCfg& cfg, hipStream_t stream) : cfg_(cfg), stream_(nullptr) {
+PeerServer::PeerServer(const PeerServerCfg& cfg, hipStream_t stream)
+    : ServerProtocol("PeerServer"), cfg_(cfg), stream_(nullptr) {
   (void)stream;  // the persistent launch gets a stream of its own (nothing else is ordered behind it)
   const int N = cfg.nworkers;
   if (N < 1 || N > kSrvMaxWorkers) throw std::invalid_argument("PeerServer: 1 .. 64 workers");
   if (!cfg.api || (!cfg.bsp && (!cfg.tracker || (!cfg.ctrl && !cfg.standin))))
     throw std::invalid_argument("PeerServer: missing host runtime handles");
-  api_ = reinterpret_cast<const HostApi*>(cfg.api);
-  if (api_->version != kHostApiVersion) throw std::runtime_error("PeerServer: host runtime C ABI version mismatch");
+  bind(cfg.api, cfg.tracker, cfg.ctrl, N, cfg.worker_timeout_s);
   if (!cfg.w || cfg.P <= 0 || cfg.K < 1 || cfg.K > 8) throw std::invalid_argument("PeerServer: weights / classes");
   if (cfg.FP != 128 && cfg.FP != 256 && cfg.FP != 512 && cfg.FP != 1024)
     throw std::invalid_argument("PeerServer: FP in {128, 256, 512, 1024}");
@@ -146,12 +142,6 @@ PeerServer::PeerServer(const PeerServerCfg& cfg, hipStream_t stream) : cfg_(cfg)
   if (cfg.bsp) a.cmd_ticks = std::max(a.cmd_ticks, a.tag_ticks + (long long)(30.0 * 1e8));
   a.spin = 1 << 22;
   ptag_.assign(N, 0u);
-  finished_.assign(N, 0);
-  failed_.assign(N, 0);
-  dead_.assign(N, 0);
-  busy_since_.assign(N, -1.0);
-  rel_k_.resize(N + 1);
-  rel_v_.resize(N + 1);
 }
 
 PeerServer::~PeerServer() {
@@ -169,10 +159,6 @@ PeerServer::~PeerServer() {
   if (ent_ring_) (void)hipHostFree(ent_ring_);
   if (err_host_) (void)hipHostFree(err_host_);
   if (tr_) (void)hipFree(tr_);
-}
-
-void PeerServer::check_api(int rc, const char* what) const {
-  if (rc < 0) throw std::runtime_error(std::string("PeerServer: ") + what + ": " + api_->last_error());
 }
 
 void PeerServer::check_device() const {
@@ -194,21 +180,6 @@ void PeerServer::check_device() const {
     if (cfg_.bsp) m += "; BSP rounds commanded " + std::to_string((long long)bsp_n_) + "; " + bsp_tags();
     throw std::runtime_error(m);
   }
-}
-
-int PeerServer::log_worker() const {
-  // server rows follow worker 0's deltas (ServerProcessor.java:154-165), or the
-  // lowest surviving worker's once 0 has failed
-  for (int j = 0; j < cfg_.nworkers; ++j)
-    if (!failed_[j]) return j;
-  return -1;
-}
-
-std::vector<int> PeerServer::failed() const {
-  std::vector<int> out;
-  for (int j = 0; j < cfg_.nworkers; ++j)
-    if (failed_[j]) out.push_back(j);
-  return out;
 }
 
 void PeerServer::launch() {
@@ -257,18 +228,14 @@ void PeerServer::write_cmd(const SrvCmd& c) {
   cmds_ = n;
 }
 
-void PeerServer::issue(int k, int64_t vc, const int* ks, const int64_t* vs, int n) {
+void PeerServer::release(int k, int64_t vc, const int* ks, const int64_t* vs, int n) {
   if (k < 0) flush_batch();  // (a release-only command: after the deltas before it)
   SrvEnt e{};
   e.k = k;
   e.dtag = k >= 0 ? (unsigned)(vc + 1) : 0u;
-  const double t = now_s();
   for (int i = 0; i < n; ++i) {
     const int j = ks[i];
-    if (j < 0 || j >= cfg_.nworkers) throw std::logic_error("PeerServer: release of an unknown worker");
-    if (finished_[j]) continue;
     e.relmask |= 1ull << j;
-    busy_since_[j] = t;
     // the replies: which worker the weights in flight are for, and their pull tag (the
     // kernel bumps a slot's tag once per release, in command / entry order)
     CtrlToken r{};
@@ -354,42 +321,6 @@ void PeerServer::flush_batch() {
   bat_slot_ = -1;
 }
 
-void PeerServer::begin() {
-  launch();
-  std::fill(finished_.begin(), finished_.end(), 0);
-  std::fill(failed_.begin(), failed_.end(), 0);
-  std::fill(busy_since_.begin(), busy_since_.end(), -1.0);
-  int n = 0;
-  for (int j = 0; j < cfg_.nworkers; ++j) {
-    int live = api().tracker_is_live((void*)cfg_.tracker, j);
-    check_api(live, "tracker is_live");
-    if (!live && !dead_[j]) {  // retired because it finished the previous run: rejoins
-      check_api(api().tracker_revive((void*)cfg_.tracker, j), "tracker revive");
-      live = 1;
-    }
-    if (!live) {
-      failed_[j] = finished_[j] = dead_[j] = 1;
-      continue;
-    }
-    const int64_t u = api().tracker_clock((void*)cfg_.tracker, j);
-    if (u > 0) api().tracker_sent((void*)cfg_.tracker, j, u);
-    rel_k_[n] = j;
-    rel_v_[n] = u;
-    ++n;
-  }
-  issue(-1, 0, rel_k_.data(), rel_v_.data(), n);  // the bootstrap (ServerProcessor.java:75-87)
-}
-
-void PeerServer::fail(int k) {
-  if (k < 0 || k >= cfg_.nworkers) throw std::out_of_range("PeerServer::fail: worker id");
-  launch();
-  failed_[k] = finished_[k] = dead_[k] = 1;
-  busy_since_[k] = -1.0;
-  const int n = api().tracker_retire((void*)cfg_.tracker, k, rel_k_.data(), rel_v_.data(), (int)rel_k_.size());
-  check_api(n, "tracker retire");
-  if (n) issue(-1, 0, rel_k_.data(), rel_v_.data(), n);
-}
-
 void PeerServer::stop() {
   if (!running_) return;
   flush_batch();  // (deltas of an open batch before the stop command)
@@ -417,19 +348,17 @@ std::vector<double> PeerServer::bench_async(int64_t deltas, int log_every) {
   if (!cfg_.standin) throw std::logic_error("PeerServer::bench_async: needs stand-in workers (cfg standin)");
   const int N = cfg_.nworkers;
   // every stand-in worker holds the weights of its clock (the bootstrap), as after begin()
-  std::fill(finished_.begin(), finished_.end(), 0);
+  reopen();
   launch();
   std::vector<int64_t> vc(N, 0);
   for (int j = 0; j < N; ++j) vc[j] = api().tracker_clock((void*)cfg_.tracker, j);
   const double t0 = now_s();
   for (int64_t i = 0; i < deltas; ++i) {
     const int k = (int)(i % N);
-    const int n = api().tracker_on_delta((void*)cfg_.tracker, k, vc[k], rel_k_.data(), rel_v_.data(), (int)rel_k_.size());
-    check_api(n, "tracker on_delta");
     // (with a metrics sink, worker 0's deltas produce the server rows, as in run())
-    issue(k, vc[k], rel_k_.data(), rel_v_.data(), n);
+    on_delta(k, vc[k], false);
     ++vc[k];
-    ++updates_;
+    set_updates(updates() + 1);
   }
   flush_batch();
   (void)log_every;
@@ -569,79 +498,6 @@ int64_t PeerServer::run_bsp_join() {
     std::rethrow_exception(e);
   }
   return bsp_ret_;
-}
-
-AsyncStatus PeerServer::run(int64_t checkpoint_every) {
-  AsyncStatus st;
-  launch();
-  const double poll = cfg_.worker_timeout_s < 1.0 ? cfg_.worker_timeout_s : 1.0;
-  for (;;) {
-    int open = 0;
-    for (int j = 0; j < cfg_.nworkers; ++j) open += !finished_[j];
-    if (open == 0) break;
-    CtrlToken t;
-    int got = 0;
-    if (!bat_.empty()) {  // an open batch takes the tokens already queued, then goes out
-      got = api().ctrl_pop((void*)cfg_.ctrl, &t, 0.0);
-      check_api(got, "token pop");
-      if (!got) {
-        flush_batch();
-        continue;
-      }
-    } else {
-      got = api().ctrl_pop((void*)cfg_.ctrl, &t, poll);
-      check_api(got, "token pop");
-    }
-    check_device();
-    if (!got) {  // watchdog: a worker holding weights that stays silent has failed
-      const double now = now_s();
-      for (int j = 0; j < cfg_.nworkers; ++j)
-        if (!finished_[j] && busy_since_[j] >= 0.0 && now - busy_since_[j] > cfg_.worker_timeout_s) {
-          st.code = kAsyncWatchdog;
-          st.worker = j;
-          st.updates = updates_;
-          return st;
-        }
-      continue;
-    }
-    const auto h0 = std::chrono::steady_clock::now();
-    ++tokens_;
-    const int k = t.worker;
-    if (k < 0 || k >= cfg_.nworkers) throw std::runtime_error("PeerServer: token from an unknown worker");
-    if (t.kind == kKindError) {
-      flush_batch();
-      st.code = kAsyncErrorToken;
-      st.worker = k;
-      st.updates = updates_;
-      return st;
-    }
-    if (finished_[k]) throw std::runtime_error("PeerServer: delta from a finished worker " + std::to_string(k));
-    busy_since_[k] = -1.0;
-    if (arrivals_.size() < kMaxArrivals) arrivals_.emplace_back(k, t.vc);
-    int n = api().tracker_on_delta((void*)cfg_.tracker, k, t.vc, rel_k_.data(), rel_v_.data(), (int)rel_k_.size());
-    check_api(n, "tracker on_delta");
-    if (t.kind == kKindFinal) {  // a finished worker no longer holds the others back
-      finished_[k] = 1;
-      const int m = api().tracker_retire((void*)cfg_.tracker, k, rel_k_.data() + n, rel_v_.data() + n,
-                                         (int)rel_k_.size() - n);
-      check_api(m, "tracker retire");
-      n += m;
-    }
-    issue(k, t.vc, rel_k_.data(), rel_v_.data(), n);
-    ++updates_;
-    ++updates_run_;
-    host_ns_ += std::chrono::duration<double, std::nano>(std::chrono::steady_clock::now() - h0).count();
-    if (checkpoint_every > 0 && updates_ % checkpoint_every == 0) {
-      stop();  // (the caller reads w: the launch must have drained)
-      st.code = kAsyncCheckpoint;
-      st.updates = updates_;
-      return st;
-    }
-  }
-  stop();
-  st.code = kAsyncDone;
-  st.updates = updates_;
-  return st;
 }
 
 }  // namespace psx
