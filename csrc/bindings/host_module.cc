@@ -224,7 +224,44 @@ PYBIND11_MODULE(_psx_host, m) {
              if (static_cast<int>(dots.size()) < num_dots(cfg.hist)) throw std::invalid_argument("too few dots");
              ctrl_step(c, cfg, f_t, dots.data(), slot);
            })
+      // the split form of step (the margins line search of the lanes round kernel):
+      // linesearch needs only (f, g.d) and returns a kLs* verdict; an accept is then
+      // accept (the gradient's dots) or accept_terminal (no dots)
+      .def("linesearch", [](Ctrl& c, const SolverCfg& cfg, double f_t, double td,
+                            int slot) { return ctrl_linesearch(c, cfg, f_t, td, slot); })
+      .def("accept",
+           [](Ctrl& c, const SolverCfg& cfg, double f_t, const std::vector<double>& dots, int slot, int verdict) {
+             if (static_cast<int>(dots.size()) < num_dots(cfg.hist)) throw std::invalid_argument("too few dots");
+             CtrlScratch ws;
+             ctrl_accept_ls(c, cfg, f_t, dots.data(), slot, verdict, ws);
+           })
+      .def("accept_terminal", [](Ctrl& c, double f_t, int slot) { ctrl_accept_terminal(c, f_t, slot); })
+      .def("accept_is_terminal",
+           [](const Ctrl& c, const SolverCfg& cfg) { return ctrl_accept_terminal_p(c, cfg); })
       .def_readonly("phase", &Ctrl::phase)
+      .def_readonly("ls_i", &Ctrl::ls_i)
+      .def_readonly("zoom", &Ctrl::zoom)
+      .def_readonly("dir_reset", &Ctrl::dir_reset)
+      .def_readonly("dg0", &Ctrl::dg0)
+      .def_readonly("gg_c", &Ctrl::gg_c)
+      .def_readonly("f_init", &Ctrl::f_init)
+      .def_readonly("gamma", &Ctrl::gamma)
+      .def_readonly("lo_t", &Ctrl::lo_t)
+      .def_readonly("lo_f", &Ctrl::lo_f)
+      .def_readonly("lo_d", &Ctrl::lo_d)
+      .def_readonly("hi_t", &Ctrl::hi_t)
+      .def_readonly("hi_f", &Ctrl::hi_f)
+      .def_readonly("hi_d", &Ctrl::hi_d)
+      .def_property_readonly("Sg", [](const Ctrl& c) { return std::vector<double>(c.Sg, c.Sg + kMaxHist); })
+      .def_property_readonly("Yg", [](const Ctrl& c) { return std::vector<double>(c.Yg, c.Yg + kMaxHist); })
+      .def_property_readonly("SY",
+                             [](const Ctrl& c) {
+                               return std::vector<double>(&c.SY[0][0], &c.SY[0][0] + kMaxHist * kMaxHist);
+                             })
+      .def_property_readonly("YY",
+                             [](const Ctrl& c) {
+                               return std::vector<double>(&c.YY[0][0], &c.YY[0][0] + kMaxHist * kMaxHist);
+                             })
       .def_readonly("action", &Ctrl::action)
       .def_readonly("action_slot", &Ctrl::action_slot)
       .def_readonly("iter", &Ctrl::iter)
@@ -247,6 +284,10 @@ PYBIND11_MODULE(_psx_host, m) {
   m.attr("kActAcceptDone") = static_cast<int>(kActAcceptDone);
   m.attr("kActDone") = static_cast<int>(kActDone);
   m.attr("kPhDone") = static_cast<int>(kPhDone);
+  m.attr("kLsTrial") = static_cast<int>(kLsTrial);
+  m.attr("kLsAccept") = static_cast<int>(kLsAccept);
+  m.attr("kLsSettle") = static_cast<int>(kLsSettle);
+  m.attr("kLsDone") = static_cast<int>(kLsDone);
 
   m.def("java_double", &java_double);
   py::class_<CsvLogger>(m, "CsvLogger")

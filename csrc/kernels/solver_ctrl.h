@@ -338,6 +338,104 @@ PSX_HD inline void ctrl_accept(Ctrl& __restrict__ c, const SolverCfg& cfg, doubl
   c.action = kActAccept;
 }
 
+// Accept the evaluated trial point when the accept ends the solve (see
+// ctrl_accept_terminal_p): no gradient dot is needed -- the new direction, the
+// curvature pair and the convergence tests of ctrl_accept all come after its
+// `done` test.  Leaves what ctrl_accept leaves on that path.
+PSX_HD inline void ctrl_accept_terminal(Ctrl& c, double f_t, int slot) {
+  c.t_acc = c.t;
+  c.iter += 1;
+  c.nacc += 1;
+  c.f_c = f_t;
+  c.action_slot = slot;
+  c.push_slot = -1;
+  c.action = kActAcceptDone;
+  c.phase = kPhDone;
+}
+
+// Would accepting the current trial end the solve before ctrl_accept reads a
+// dot?  (The last iteration.  A caller that cannot continue either way -- no
+// evaluation slot left -- may take ctrl_accept_terminal as well: it then skips
+// pair bookkeeping that nothing reads after the end.)
+PSX_HD inline bool ctrl_accept_terminal_p(const Ctrl& c, const SolverCfg& cfg) { return c.iter + 1 >= cfg.iters; }
+
+// Verdict of the line search on one evaluation (ctrl_linesearch).
+enum LsVerdict : int {
+  kLsTrial = 0,   // evaluate phi at the new c.t (action kActTrial)
+  kLsAccept = 1,  // strong Wolfe holds at c.t: the caller accepts
+  kLsSettle = 2,  // budget spent, sufficient decrease at c.t: the caller accepts
+  kLsDone = 3,    // budget spent without decrease: finished without moving (action kActDone)
+};
+
+// The line search on phi(t) = f(x + t d) (L-BFGS mode, phase kPhLS): needs only
+// phi(c.t) = f_t and phi'(c.t) = td = g_t . d.  Counts the evaluation, moves the
+// bracket / zoom state and the budgets, and either sets the next trial step or
+// tells the caller to accept (ctrl_accept_ls with the gradient's dots, or
+// ctrl_accept_terminal) -- the accepted step is c.t.
+PSX_HD inline int ctrl_linesearch(Ctrl& __restrict__ c, const SolverCfg& cfg, double f_t, double td, int slot) {
+  c.evals += 1;
+  const bool finite = f_t == f_t && fabs(f_t) < 1e300;
+  c.action_slot = slot;
+  const double c1 = 1e-4, c2 = 0.9;
+  const double t = c.t;
+  const double dd = td;
+  c.ls_i += 1;
+  const bool armijo = finite && f_t <= c.f_c + c1 * t * c.dg0;
+  double tn = t;
+  if (!c.zoom) {
+    if (!finite) {
+      tn = t * 0.5;
+    } else if (!armijo || (f_t >= c.lo_f && c.ls_i > 1)) {
+      c.hi_t = t; c.hi_f = f_t; c.hi_d = dd;
+      c.zoom = 1;
+      tn = ls_interp(c.lo_t, c.lo_f, c.lo_d, c.hi_t, c.hi_f, c.hi_d);
+    } else if (fabs(dd) <= c2 * fabs(c.dg0)) {
+      return kLsAccept;
+    } else if (dd >= 0.0) {
+      c.hi_t = c.lo_t; c.hi_f = c.lo_f; c.hi_d = c.lo_d;
+      c.lo_t = t; c.lo_f = f_t; c.lo_d = dd;
+      c.zoom = 1;
+      tn = ls_interp(c.lo_t, c.lo_f, c.lo_d, c.hi_t, c.hi_f, c.hi_d);
+    } else {
+      c.lo_t = t; c.lo_f = f_t; c.lo_d = dd;
+      tn = t * 1.5;
+    }
+  } else {
+    if (!armijo || f_t >= c.lo_f) {
+      c.hi_t = t; c.hi_f = f_t; c.hi_d = dd;
+    } else {
+      if (fabs(dd) <= c2 * fabs(c.dg0)) return kLsAccept;
+      if (dd * (c.hi_t - c.lo_t) >= 0.0) {
+        c.hi_t = c.lo_t; c.hi_f = c.lo_f; c.hi_d = c.lo_d;
+      }
+      c.lo_t = t; c.lo_f = f_t; c.lo_d = dd;
+    }
+    tn = ls_interp(c.lo_t, c.lo_f, c.lo_d, c.hi_t, c.hi_f, c.hi_d);
+  }
+  const bool out_of_slots = slot + 1 >= cfg.nslots;
+  if (c.ls_i >= cfg.ls_max || out_of_slots) {
+    c.ls_fail += 1;
+    if (armijo && f_t < c.f_c) return kLsSettle;  // settle for sufficient decrease
+    c.action = kActDone;
+    c.phase = kPhDone;
+    return kLsDone;
+  }
+  c.t = tn;
+  c.action = kActTrial;
+  return kLsTrial;
+}
+
+// The accept that follows a kLsAccept / kLsSettle verdict, from the gradient's dots.
+PSX_HD inline void ctrl_accept_ls(Ctrl& __restrict__ c, const SolverCfg& cfg, double f_t,
+                                  const double* __restrict__ dots, int slot, int verdict, CtrlScratch& __restrict__ ws) {
+  ctrl_accept(c, cfg, f_t, dots, slot, ws);
+  // (a settle in the last slot: nothing can follow, whatever ctrl_accept decided)
+  if (verdict == kLsSettle && slot + 1 >= cfg.nslots && c.phase != kPhDone) {
+    c.action = kActAcceptDone;
+    c.phase = kPhDone;
+  }
+}
+
 // Advance the state machine after the function evaluation of `slot`.
 // f_t = objective at the trial point, dots as documented above.
 // (__restrict__: the state, the dots and the scratch never alias -- on the device
@@ -345,8 +443,13 @@ PSX_HD inline void ctrl_accept(Ctrl& __restrict__ c, const SolverCfg& cfg, doubl
 // wait behind its own stores)
 PSX_HD inline void ctrl_step(Ctrl& __restrict__ c, const SolverCfg& cfg, double f_t, const double* __restrict__ dots,
                              int slot, CtrlScratch& __restrict__ ws) {
+  if (c.phase == kPhLS && cfg.mode != kModeGD) {
+    const int v = ctrl_linesearch(c, cfg, f_t, dots[1], slot);
+    if (v == kLsAccept || v == kLsSettle) ctrl_accept_ls(c, cfg, f_t, dots, slot, v, ws);
+    return;
+  }
   c.evals += 1;
-  const double tt = dots[0], td = dots[1];
+  const double tt = dots[0];
   const bool finite = f_t == f_t && fabs(f_t) < 1e300;
   if (c.phase == kPhDone) return;
   if (c.phase == kPhInit) {
@@ -375,69 +478,9 @@ PSX_HD inline void ctrl_step(Ctrl& __restrict__ c, const SolverCfg& cfg, double 
     c.action = kActInit;
     return;
   }
-  // ---- line search on phi(t) = f(x + t d) ----
+  // ---- mode GD: every evaluation is accepted ----
   c.action_slot = slot;
-  if (cfg.mode == kModeGD) {
-    ctrl_accept(c, cfg, f_t, dots, slot, ws);
-    return;
-  }
-  const double c1 = 1e-4, c2 = 0.9;
-  const double t = c.t;
-  const double dd = td;
-  c.ls_i += 1;
-  const bool armijo = finite && f_t <= c.f_c + c1 * t * c.dg0;
-  double tn = t;
-  if (!c.zoom) {
-    if (!finite) {
-      tn = t * 0.5;
-    } else if (!armijo || (f_t >= c.lo_f && c.ls_i > 1)) {
-      c.hi_t = t; c.hi_f = f_t; c.hi_d = dd;
-      c.zoom = 1;
-      tn = ls_interp(c.lo_t, c.lo_f, c.lo_d, c.hi_t, c.hi_f, c.hi_d);
-    } else if (fabs(dd) <= c2 * fabs(c.dg0)) {
-      ctrl_accept(c, cfg, f_t, dots, slot, ws);
-      return;
-    } else if (dd >= 0.0) {
-      c.hi_t = c.lo_t; c.hi_f = c.lo_f; c.hi_d = c.lo_d;
-      c.lo_t = t; c.lo_f = f_t; c.lo_d = dd;
-      c.zoom = 1;
-      tn = ls_interp(c.lo_t, c.lo_f, c.lo_d, c.hi_t, c.hi_f, c.hi_d);
-    } else {
-      c.lo_t = t; c.lo_f = f_t; c.lo_d = dd;
-      tn = t * 1.5;
-    }
-  } else {
-    if (!armijo || f_t >= c.lo_f) {
-      c.hi_t = t; c.hi_f = f_t; c.hi_d = dd;
-    } else {
-      if (fabs(dd) <= c2 * fabs(c.dg0)) {
-        ctrl_accept(c, cfg, f_t, dots, slot, ws);
-        return;
-      }
-      if (dd * (c.hi_t - c.lo_t) >= 0.0) {
-        c.hi_t = c.lo_t; c.hi_f = c.lo_f; c.hi_d = c.lo_d;
-      }
-      c.lo_t = t; c.lo_f = f_t; c.lo_d = dd;
-    }
-    tn = ls_interp(c.lo_t, c.lo_f, c.lo_d, c.hi_t, c.hi_f, c.hi_d);
-  }
-  const bool out_of_slots = slot + 1 >= cfg.nslots;
-  if (c.ls_i >= cfg.ls_max || out_of_slots) {
-    c.ls_fail += 1;
-    if (armijo && f_t < c.f_c) {  // settle for sufficient decrease
-      ctrl_accept(c, cfg, f_t, dots, slot, ws);
-      if (out_of_slots && c.phase != kPhDone) {
-        c.action = kActAcceptDone;
-        c.phase = kPhDone;
-      }
-      return;
-    }
-    c.action = kActDone;
-    c.phase = kPhDone;
-    return;
-  }
-  c.t = tn;
-  c.action = kActTrial;
+  ctrl_accept(c, cfg, f_t, dots, slot, ws);
 }
 
 // Convenience overload with a stack workspace (host code, tests).
