@@ -130,7 +130,8 @@ def build_hip(force=False, jobs=8):
     headers = sorted(glob.glob(os.path.join(CSRC, "kernels", "*.h")) + glob.glob(os.path.join(CSRC, "solver", "*.h")) +
                      glob.glob(os.path.join(CSRC, "comm", "*.h")) + glob.glob(os.path.join(CSRC, "runtime", "*.h")) +
                      [os.path.join(CSRC, "host", "capi.h"), os.path.join(CSRC, "host", "ctrl.h"),
-                     os.path.join(CSRC, "host", "sink_record.h"), os.path.join(CSRC, "host", "server_protocol.h")])
+                     os.path.join(CSRC, "host", "sink_record.h"), os.path.join(CSRC, "host", "server_protocol.h"),
+                     os.path.join(CSRC, "host", "lanes_protocol.h")])
     out = os.path.join(PKG, "_psx_hip" + _ext_suffix())
     cflags = [
         "-O3",
@@ -154,7 +155,7 @@ def build_selftest(sanitize: str = "address,undefined", force=False):
     """Host-runtime self-test binary (csrc/tests/host_selftest.cc) under a
     sanitizer: "address,undefined" or "thread" (SURVEY.md §5.2)."""
     sources = [os.path.join(CSRC, "tests", "host_selftest.cc")] + sorted(glob.glob(os.path.join(CSRC, "host", "*.cc")))
-    headers = sorted(glob.glob(os.path.join(CSRC, "host", "*.h")))
+    headers = sorted(glob.glob(os.path.join(CSRC, "host", "*.h"))) + [os.path.join(CSRC, "kernels", "lanes_records.h")]
     tag = sanitize.replace(",", "_")
     out = os.path.join(ROOT, "build", "selftest", f"host_selftest_{tag}")
     flags = ["-O1", "-g", "-std=c++17", f"-fsanitize={sanitize}", "-fno-omit-frame-pointer"]

@@ -33,6 +33,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "lanes_records.h"
 #include "lr_kernels.h"
 #include "solve_kernels.h"
 
@@ -65,17 +66,6 @@ struct LaneDev {
   float* loss2;       // [kLaneBufs] training loss by round buffer
   Ctrl* ctrl;         // the lane's controller after the round (host diagnostics)
   float* wpull;       // [P] overlapped launches: the lane's copy of the pulled weights (LanesArgs::ovl)
-};
-
-// Per-round arguments of one lane: the window and the new rows of this round:
-// dataset rows first + i * step (i < n) into ring slots (dst + i) % cap, then (a
-// delivery that wraps the worker's shard) first2 + i * step (i < n2) into slots
-// (dst + n + i) % cap.
-struct LaneRound {
-  int B, start, n, dst;
-  long long first, step, first2;
-  int n2;
-  int delay_us;  // BSP round kernel: injected straggler delay before the lane's solve (0: none)
 };
 
 struct EvalModel {
@@ -260,63 +250,7 @@ void launch_lanes_eval(const SolverCfg& cfg, const EvalMulti& ev, hipStream_t s)
 //     global model after its own update on the logging lane (the server row) --
 //     with its own 32 workgroups right after its push, and publishes the counts
 //     as tagged 16-B chunks (no store-completion wait on the lane's path).
-// Host <-> device records are 16-B chunks {tag, 3 x u32 payload}: a chunk is
-// written by ONE 16-B store, so a reader that sees every chunk carry the
-// expected tag has the whole record, without ordering between the stores.
-struct alignas(16) TagChunk {
-  unsigned tag, a, b, c;
-};
-constexpr int kRelChunks = 8;
-struct alignas(16) AsyncRelease {  // host -> lane (pinned), tag = the lane's record count
-  TagChunk ch[kRelChunks];
-};
-// release record payload (unpacked on both sides by the same layout)
-struct RelRec {
-  int stop;              // 1: leave the launch (no solve)
-  long long vc;          // the pulled weights' version (tracker clock)
-  long long snap;        // ticket whose snapshot holds the pulled weights
-  LaneRound r;           // window + this solve's new stream rows
-  unsigned long long slot_w, slot_s;  // pinned EvalSlot addresses (0: no row)
-  unsigned seq_w, seq_s;              // their sequence numbers (low 32 bits)
-  int delay_us;          // injected straggler delay before the push (tests)
-  unsigned pull_tag;     // peer data plane: the receive slot's tag that carries these weights
-};
-PSX_HD inline void pack_release(const RelRec& q, unsigned tag, TagChunk* ch) {
-  auto lo = [](long long v) { return (unsigned)(unsigned long long)v; };
-  auto hi = [](long long v) { return (unsigned)((unsigned long long)v >> 32); };
-  ch[0] = TagChunk{tag, (unsigned)q.stop, lo(q.vc), hi(q.vc)};
-  ch[1] = TagChunk{tag, lo(q.snap), hi(q.snap), (unsigned)q.r.B};
-  ch[2] = TagChunk{tag, (unsigned)q.r.start, (unsigned)q.r.n, (unsigned)q.r.dst};
-  ch[3] = TagChunk{tag, lo(q.r.first), hi(q.r.first), (unsigned)q.r.n2};
-  ch[4] = TagChunk{tag, lo(q.r.step), hi(q.r.step), lo(q.r.first2)};
-  ch[5] = TagChunk{tag, hi(q.r.first2), lo((long long)q.slot_w), hi((long long)q.slot_w)};
-  ch[6] = TagChunk{tag, q.seq_w, lo((long long)q.slot_s), hi((long long)q.slot_s)};
-  ch[7] = TagChunk{tag, q.seq_s, (unsigned)q.delay_us, q.pull_tag};
-}
-PSX_HD inline void unpack_release(const TagChunk* ch, RelRec& q) {
-  auto j = [](unsigned l, unsigned h) { return (long long)(((unsigned long long)h << 32) | l); };
-  q.stop = (int)ch[0].a;
-  q.vc = j(ch[0].b, ch[0].c);
-  q.snap = j(ch[1].a, ch[1].b);
-  q.r.B = (int)ch[1].c;
-  q.r.start = (int)ch[2].a;
-  q.r.n = (int)ch[2].b;
-  q.r.dst = (int)ch[2].c;
-  q.r.first = j(ch[3].a, ch[3].b);
-  q.r.n2 = (int)ch[3].c;
-  q.r.step = j(ch[4].a, ch[4].b);
-  q.r.first2 = j(ch[4].c, ch[5].a);
-  q.slot_w = (unsigned long long)j(ch[5].b, ch[5].c);
-  q.seq_w = ch[6].a;
-  q.slot_s = (unsigned long long)j(ch[6].b, ch[6].c);
-  q.seq_s = ch[7].a;
-  q.delay_us = (int)ch[7].b;
-  q.pull_tag = ch[7].c;
-  q.r.delay_us = 0;
-}
-// token: lane -> host (pinned ring, slot t % ring): {tag = ticket (low 32 bits,
-// tickets start at 1), lane, vc low, vc high}
-typedef TagChunk AsyncToken;
+// The records (release record, token) and their 16-B chunks: lanes_records.h.
 // the tag of a tagged evaluation slot's chunks (never 0)
 PSX_HD inline unsigned eval_tag(unsigned long long seq) { return (unsigned)seq | 0x80000000u; }
 

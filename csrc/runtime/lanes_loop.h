@@ -27,6 +27,12 @@
 //   * the vector-clock tracker advances one round; the device error word (pinned)
 //     is polled: a timed-out cross-workgroup wait surfaces as an exception naming
 //     the round.
+//
+// The asynchronous loops (run_async, run_async_remote): what they decide -- who
+// starts with which clock and rows, budgets, injected failures, FINAL, the
+// watchdogs -- is csrc/host/lanes_protocol.h (HIP-free, pinned on the CPU by
+// csrc/tests/host_selftest.cc); this class is its plane: the workspace, the
+// persistent launch, the pinned records, the events and the transport.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -37,26 +43,20 @@
 #include "../comm/comm.h"
 #include "async_server.h"
 #include "../host/capi.h"
+#include "../host/lanes_protocol.h"
 #include "../kernels/lanes_kernels.h"
 
 namespace psx {
 
-struct LanesLoopCfg {
+// (the producer, the lanes' worker ids and windows, sink / tracker / api handles, the
+// cadence, log_worker and delay_us: LanesHostCfg, csrc/host/lanes_protocol.h)
+struct LanesLoopCfg : LanesHostCfg {
   SolverCfg scfg;  // K, F, Fp, P, cap, iters, hist, ls_max, mode, center, zero_const, nslots, gd_lr, tol
-  // producer: worker k of N reads dataset rows k, k + N, ... (`epochs` passes)
+  // the resident dataset the producer reads
   const uint16_t* dsX = nullptr;
   const int32_t* dsy = nullptr;
-  int64_t ds_rows = 0;
-  int N = 1;              // logical workers in the whole job
-  int per_iter_rows = 0;  // > 0: rows per round; 0: the producer clock p_ms
-  double p_ms = 0.0;
-  int64_t epochs = 1;
-  double t0_ms = 0.0;
-  // lanes of this process
-  int L = 0;
-  std::vector<int> k;             // worker ids
+  // per lane
   std::vector<uintptr_t> X, XT, y;  // rings [cap][Fp] bf16 (+ optional feature-major copy, kept in step), labels
-  std::vector<uintptr_t> window;  // SlidingWindow*
   // server state (replica): w [P], its evaluation fragments (two buffers, columns scoff..)
   float* w = nullptr;
   float lr = 1.f;
@@ -74,42 +74,23 @@ struct LanesLoopCfg {
   const uint16_t* Ti = nullptr;
   const uint16_t* Tv = nullptr;
   int tnz = 0;
-  uintptr_t sink = 0;       // MetricsSink* (0: no rows)
-  bool log_server = true;   // server rows on this rank
-  bool log_workers = true;  // worker rows on this rank
-  uintptr_t tracker = 0;    // VectorClockTracker* (0: none)
-  uintptr_t api = 0;        // HostApi*
   int server_rank = 0;      // multi-rank: the rank that applies the update
   // multi-rank schedule: false = reduce to the server rank, update there, broadcast
   // the weights (the PS push / pull); true = all-reduce of the lane sums, every rank
   // applies the same update to its replica (one collective per round)
   bool allreduce = false;
-  // stream-driven cadence (the CLI's --iter_new_rows / --iter_new_frac / --iter_new_cap,
-  // psx/runtime/config.py:new_tuples_needed): a round starts once every lane saw at
-  // least max(new_rows, min(ceil(new_frac * window), new_cap)) new tuples since its
-  // last solve (or its stream ended); 0 / 0.0: every round solves at once
-  int new_rows = 0;
-  double new_frac = 0.0;
-  int new_cap = 0;
-  // ... capped at new_ramp << (the lane's completed solves) for its first solves (0: off)
-  int new_ramp = 0;
-  // asynchronous consistency (run_async): the worker whose deltas produce the
-  // server rows (ServerProcessor.java:154: worker 0, or the lowest live one;
-  // -1: none) and injected straggler delays per lane (us, tests / fault injection)
-  int log_worker = 0;
-  std::vector<int> delay_us;
   // first XCD of this process's lanes (lane l on XCD xcd0 + l): processes that
   // share one GPU (IpcComm) take disjoint XCDs
   int xcd0 = 0;
 };
 
-class LanesLoop {
+class LanesLoop : private AsyncLanesPlane {
  public:
   // comm: the multi-rank job's transport (RcclComm: one rank per GPU; IpcComm:
   // ranks sharing one GPU) -- nullptr: one rank.  A rank with L == 0 is a
   // dedicated server rank.
   LanesLoop(const LanesLoopCfg& cfg, Comm* comm);
-  ~LanesLoop();
+  ~LanesLoop() override;
   LanesLoop(const LanesLoop&) = delete;
   LanesLoop& operator=(const LanesLoop&) = delete;
   // Run `rounds` rounds from round r0; returns the rounds run (fewer when every
@@ -182,34 +163,35 @@ class LanesLoop {
   void set_trace(int cap);
   std::vector<std::vector<int64_t>> trace_take(hipStream_t s);
   std::vector<int64_t> clock_ref(hipStream_t s);
-  const std::vector<int>& crashed() const { return crashed_; }
-  const std::vector<int>& left() const { return left_; }
+  const std::vector<int>& crashed() const { return proto_.crashed(); }
+  const std::vector<int>& left() const { return proto_.left(); }
   // Debug (tests): every applied ticket's delta into buf [cap][P] (device, slot (t - 1) %
   // cap) and a host log per ticket of what the release that solved it carried:
   // {ticket, lane, worker, vc, snapshot ticket, B, start, first, step, n, first2, n2}
   void set_async_debug(uintptr_t buf, int cap) {
     dbg_delta_ = reinterpret_cast<float*>(buf);
     dbg_cap_ = cap;
+    proto_.set_log(dbg_delta_ != nullptr);
   }
-  const std::vector<std::vector<int64_t>>& async_log() const { return alog_; }
+  const std::vector<std::vector<int64_t>>& async_log() const { return proto_.log(); }
   // Allocate (and zero) the asynchronous workspace now: ranks sharing one GPU do this
   // before any rank's persistent launch holds CUs a fill kernel would wait for.  With
   // the peer data plane also one empty launch (every lane stopped at once) that drains
   // here: the first launch's one-time device work (the code object's load, the
   // runtime's copy paths) must not wait behind another rank's persistent launch.
   void prepare_async();
-  int64_t tickets() const { return (int64_t)aticket_; }  // deltas applied by the asynchronous loop so far
-  double host_us_per_update() const { return async_updates_ ? async_ns_ / 1000.0 / (double)async_updates_ : 0.0; }
+  int64_t tickets() const { return (int64_t)proto_.tickets(); }  // deltas applied by the asynchronous loop so far
+  double host_us_per_update() const { return proto_.host_us_per_update(); }
   // host time spent per consumed token (token seen -> its rows handed over, tracker, the
   // releases it triggers written): the host loop's share of an asynchronous update
-  double host_busy_us_per_token() const { return tok_n_ ? tok_ns_ / 1000.0 / (double)tok_n_ : 0.0; }
+  double host_busy_us_per_token() const { return proto_.host_busy_us_per_token(); }
   // Evaluate the last round's rows (one launch of riders only).
   void flush(hipStream_t stream);
   void set_sink(uintptr_t sink) { cfg_.sink = sink; }
   // Idle waits of run_async / run_async_remote (a row-starved stream, a lane waiting for
   // its release): this bound, never below the in-flight watchdog max_wait_s (the CLI's
   // --idle_wait; default 600 s).  A short --worker_timeout then only bounds busy workers.
-  void set_idle_wait(double s) { idle_wait_s_ = s > 0.0 ? s : 600.0; }
+  void set_idle_wait(double s) { proto_.set_idle_wait(s); }
   void set_lr(float lr) { cfg_.lr = lr; }
   int64_t next_local(int lane) const { return next_local_.at(lane); }
   void set_next_local(int lane, int64_t v) { next_local_.at(lane) = v; }
@@ -217,7 +199,9 @@ class LanesLoop {
   int64_t seen_at_solve(int lane) const { return seen_at_solve_.at(lane); }
   void set_seen_at_solve(int lane, int64_t v) { seen_at_solve_.at(lane) = v; }
   // new tuples lane windows of `size` rows wait for (0: no cadence)
-  int64_t new_tuples_needed(int64_t size, int64_t updates = -1) const;  // updates < 0: no ramp
+  int64_t new_tuples_needed(int64_t size, int64_t updates = -1) const {  // updates < 0: no ramp
+    return cfg_.new_tuples_needed(size, updates);
+  }
   bool exhausted(int lane) const { return next_local_[lane] >= local_total_[lane] * cfg_.epochs; }
   bool all_exhausted() const;
   int hand_off_scope() const { return S_; }  // 2: one-XCD hand-offs, 1: sc1 (placement check failed)
@@ -259,7 +243,7 @@ class LanesLoop {
   }
   // Raise if a lane's solve reported a timed-out cross-workgroup wait (the pinned
   // error words; no synchronisation: call after one to cover every enqueued round).
-  void poll_errors() { check_errors(-1); }
+  void poll_errors() override { check_errors(-1); }
   // phase timeline of lane `lane`'s last solve (PSX_LANES_STAMPS=1 at construction):
   // [slot][k] s_memrealtime ticks (100 MHz), row 30 = the round's own phases
   std::vector<long long> read_stamps(int lane, hipStream_t stream) const;
@@ -291,15 +275,19 @@ class LanesLoop {
   int fill_lane_eval(LanesArgs* a, int64_t r, int par, const std::vector<int64_t>& seen, SinkRecord* recs);
   void check_errors(int64_t round);
   int rider_count(int nmodels, int L) const;
-  // ---- asynchronous loop ----
+  // ---- asynchronous loops: the plane of proto_ (AsyncLanesPlane) ----
   void ensure_async();
-  int64_t poll_async(int lane, double now_ms);  // due rows -> window + the lane's pending runs
-  bool try_release(int lane, int64_t vc, double now_ms, int64_t snap = -1);
   void launch_async(hipStream_t stream, bool remote);
-  void write_release(int lane, const RelRec& q);
-  void stop_all(hipStream_t stream);
-  void stop_lane(int l);  // lane l's stop record (once per launch)
-  std::string launch_report();  // (failure reports) the persistent launch's progress
+  void stop_all(hipStream_t stream);  // every lane's stop record, then the launch drains
+  // launch, `loop`, drain -- also behind an exception of the loop -- and the final error poll
+  template <class Loop>
+  int64_t serve_async(hipStream_t stream, bool remote, int64_t t_begin, Loop loop);
+  void write_release(int lane, const RelRec& q, unsigned tag) override;
+  AsyncToken read_token(uint64_t n) override;
+  std::string progress_report() override;  // the persistent launch's progress
+  void begin_pull(int lane) override;
+  bool pull_done(int lane) override;
+  void send_delta(int lane) override;
 
   LanesLoopCfg cfg_;
   Comm* comm_;
@@ -371,45 +359,23 @@ class LanesLoop {
   AsyncToken* tok_host_ = nullptr;      // pinned [ring]
   AsyncArgs aargs_{};
   int R_ = 64, ring_ = 64;
-  uint64_t aticket_ = 0;                // last ticket applied (device counter mirror)
-  std::vector<uint64_t> relc_;          // release records written per lane
-  std::vector<LaneRound> pend_r_;       // new stream rows not yet in the lane's ring
-  enum { kIdle = 0, kWant = 1, kRunning = 2, kGone = 6 };
-  std::vector<int> state_;
-  std::vector<int64_t> inj_crash_, inj_stop_;  // set_injection (consumed by the next run_async)
-  bool inj_drop_ = true;
-  std::vector<int> crashed_, left_;             // workers that crashed / left in the last run
+  AsyncLanesProtocol proto_;            // the loops' host logic and state (bound by ensure_async)
   long long* tr_ = nullptr;                     // set_trace ring (device)
   int tr_cap_ = 0;
   int64_t tr_n_ = 0, tr_taken_ = 0;             // BSP rounds recorded / taken
   std::vector<int64_t> tr_round_;               // round of each BSP ring slot
   uint64_t tr_tick_ = 0;                        // asynchronous: last ticket taken
-  std::vector<uint8_t> lane_stopped_;           // lanes already sent their stop record (this launch)
-  std::vector<int64_t> want_vc_;
-  struct RunRec {
-    int64_t vc = 0, nseen = 0;
-    int slot_w = -1, slot_s = -1;
-    uint64_t seq_w = 0, seq_s = 0;
-    int64_t snap = 0;  // the pulled snapshot's ticket
-    LaneRound r{};     // the window + new rows of the release
-  };
   float* dbg_delta_ = nullptr;
   int dbg_cap_ = 0;
-  std::vector<std::vector<int64_t>> alog_;
-  std::vector<RunRec> runrec_;
-  std::vector<int> lane_of_;            // worker id -> lane (-1: not on this loop)
-  int log_lane_ = -1;
   int64_t launch_no_ = 0;
-  double rel_wait_s_ = 60.0;  // the lanes' release / pull wait budget of the current run (device)
-  double idle_wait_s_ = 600.0;  // set_idle_wait
   std::vector<hipEvent_t> pull_ev_;     // remote mode: a lane's weights received
-  // peer data plane (set_peer): receive region, per-lane inbox slots, the pull tag of
-  // each lane's pending release
+  P2P* rp2p_ = nullptr;                 // the host transport of the current run_async_remote
+  hipStream_t rcs_ = nullptr;           // ... and its stream
+  // peer data plane (set_peer): receive region, per-lane inbox slots
   float* peer_rx_ = nullptr;
   unsigned* peer_rx_tag_ = nullptr;
   int64_t peer_stride_ = 0;
   std::vector<uintptr_t> peer_inbox_, peer_inbox_tag_;
-  std::vector<unsigned> pull_tag_;
   // peer_sum BSP (set_peer_sum)
   const float* psum_rx_ = nullptr;
   const unsigned* psum_rx_tag_ = nullptr;
@@ -422,10 +388,6 @@ class LanesLoop {
   // ordered after / before the caller's stream by events
   hipStream_t astream_ = nullptr;
   hipEvent_t aev_in_ = nullptr, aev_out_ = nullptr;
-  int64_t async_updates_ = 0;
-  double async_ns_ = 0.0;
-  int64_t tok_n_ = 0;
-  double tok_ns_ = 0.0;
 };
 
 }  // namespace psx

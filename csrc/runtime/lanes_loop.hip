@@ -608,17 +608,6 @@ void LanesLoop::check_errors(int64_t round) {
   }
 }
 
-int64_t LanesLoop::new_tuples_needed(int64_t size, int64_t updates) const {
-  int64_t k = (int64_t)std::ceil(cfg_.new_frac * (double)size);  // as math.ceil in config.py
-  if (k < 0) k = 0;
-  if (cfg_.new_cap > 0 && k > cfg_.new_cap) k = cfg_.new_cap;
-  if (cfg_.new_ramp > 0 && updates >= 0 && updates < 30) {  // the first solves come early
-    const int64_t r = (int64_t)cfg_.new_ramp << updates;
-    if (k > r) k = r;
-  }
-  return k > cfg_.new_rows ? k : cfg_.new_rows;
-}
-
 int64_t LanesLoop::run(int64_t rounds, int64_t r0, hipStream_t stream, double max_wait_s, double deadline_ms) {
   const int64_t t_begin = steady_ns();
   const int L = cfg_.L;
@@ -1102,96 +1091,12 @@ void LanesLoop::ensure_async() {
   a.Tv = cfg_.Tv;
   a.tnz = (cfg_.Ti && cfg_.Tv && cfg_.tnz > 0 && cfg_.tnz % 8 == 0) ? cfg_.tnz : 0;
   a.claim = claim_;
-  relc_.assign(L, 0);
-  pend_r_.assign(L, LaneRound{});
-  state_.assign(L, kIdle);
-  want_vc_.assign(L, 0);
-  runrec_.assign(L, RunRec{});
-  lane_of_.assign(cfg_.N, -1);
-  for (int l = 0; l < L; ++l) lane_of_.at(cfg_.k[l]) = l;
+  proto_.bind(&cfg_, s.cap, peer_rx_ != nullptr, this, &local_total_, &next_local_, &seen_at_solve_, &times_);
 }
 
-namespace {
-// the pending new rows of a lane as <= 2 contiguous runs (LaneRound n / n2)
-void drop_front(LaneRound& r, int64_t d, int64_t cap) {
-  while (d > 0 && r.n > 0) {
-    const int64_t k = d < r.n ? d : r.n;
-    r.first += k * r.step;
-    r.dst = (int)((r.dst + k) % cap);
-    r.n -= (int)k;
-    d -= k;
-    if (r.n == 0 && r.n2 > 0) {
-      r.first = r.first2;
-      r.n = r.n2;
-      r.n2 = 0;
-    }
-  }
-}
-void append_run(LaneRound& r, long long src_first, long long step, int64_t slot, int64_t run, int64_t cap) {
-  if (r.n == 0) {
-    r.first = src_first;
-    r.step = step;
-    r.n = (int)run;
-    r.dst = (int)slot;
-    r.n2 = 0;
-    return;
-  }
-  if ((r.dst + r.n + r.n2) % cap != slot) throw std::logic_error("LanesLoop: ring slots of a delivery not contiguous");
-  if (r.n2 == 0 && src_first == r.first + (long long)r.n * r.step)
-    r.n += (int)run;
-  else if (r.n2 > 0 && src_first == r.first2 + (long long)r.n2 * r.step)
-    r.n2 += (int)run;
-  else if (r.n2 == 0) {
-    r.first2 = src_first;
-    r.n2 = (int)run;
-  } else {
-    throw std::logic_error("LanesLoop: pending rows of a release span three runs");
-  }
-}
-}  // namespace
-
-int64_t LanesLoop::poll_async(int lane, double now_ms) {
-  if (exhausted(lane)) return 0;
-  const int k = cfg_.k[lane];
-  const int64_t lt = local_total_[lane];
-  int64_t& nl = next_local_[lane];
-  const int64_t limit = lt * cfg_.epochs - nl;
-  int64_t n;
-  if (cfg_.per_iter_rows > 0) {
-    n = cfg_.per_iter_rows < limit ? cfg_.per_iter_rows : limit;
-    times_.assign((size_t)n, now_ms);
-  } else {
-    const int64_t epoch = nl / lt, cur = nl - epoch * lt;
-    int64_t mx = limit < lt - cur ? limit : lt - cur;
-    if (mx > (int64_t(1) << 22)) mx = int64_t(1) << 22;
-    times_.resize(mx > 0 ? (size_t)mx : 1);
-    n = api().due_rows(k, cfg_.N, cfg_.p_ms, cfg_.ds_rows, cur, now_ms, mx, times_.data());
-    check(n, "due_rows");
-  }
-  if (n <= 0) return 0;
-  const int64_t first = api().window_insert_many(reinterpret_cast<void*>(cfg_.window[lane]), times_.data(), n);
-  check(first, "window insert");
-  const int64_t cap = cfg_.scfg.cap;
-  const int64_t keep = n < cap ? n : cap, skip = n - keep;
-  LaneRound& r = pend_r_[lane];
-  const int64_t tot = (int64_t)r.n + r.n2 + keep;
-  if (tot > cap) drop_front(r, tot - cap, cap);  // rows the ring overwrites before the next solve
-  int64_t slot = (first + skip) % cap, pos = nl + skip, remaining = keep;
-  while (remaining > 0) {  // split at the shard's epoch boundaries
-    const int64_t cur = pos % lt;
-    const int64_t run = remaining < lt - cur ? remaining : lt - cur;
-    append_run(r, k + cur * (int64_t)cfg_.N, cfg_.N, slot, run, cap);
-    slot = (slot + run) % cap;
-    pos += run;
-    remaining -= run;
-  }
-  nl += n;
-  return n;
-}
-
-void LanesLoop::write_release(int lane, const RelRec& q) {
+void LanesLoop::write_release(int lane, const RelRec& q, unsigned tag) {
   TagChunk ch[kRelChunks];
-  pack_release(q, (unsigned)(++relc_[lane]), ch);
+  pack_release(q, tag, ch);
   volatile TagChunk* dst = rel_host_[lane].ch;
   for (int i = 0; i < kRelChunks; ++i) {
     __m128i v;
@@ -1201,57 +1106,13 @@ void LanesLoop::write_release(int lane, const RelRec& q) {
   std::atomic_thread_fence(std::memory_order_release);
 }
 
-bool LanesLoop::try_release(int lane, int64_t vc, double now_ms, int64_t snap) {
-  poll_async(lane, now_ms);
-  int64_t size = 0, start = 0, sn = 0;
-  check(api().window_state(reinterpret_cast<void*>(cfg_.window[lane]), &size, &start, &sn), "window state");
-  const int64_t need = new_tuples_needed(size, vc);  // (vc: the worker's completed pushes)
-  if (!(size > 0 && (need <= 0 || sn - seen_at_solve_[lane] >= need || exhausted(lane)))) return false;
-  seen_at_solve_[lane] = sn;
-  RelRec q;
-  std::memset(&q, 0, sizeof(q));
-  q.vc = vc;
-  // the weights right after the latest applied update (remote: the lane's receive slot)
-  q.snap = snap >= 0 ? (long long)snap : (long long)aticket_;
-  q.r = pend_r_[lane];
-  q.r.B = (int)size;
-  q.r.start = (int)start;
-  if (q.r.n == 0) q.r.step = cfg_.N;
-  pend_r_[lane] = LaneRound{};
-  RunRec& rr = runrec_[lane];
-  rr = RunRec{};
-  rr.vc = vc;
-  rr.nseen = sn;
-  rr.snap = q.snap;
-  rr.r = q.r;
-  if (cfg_.sink) {
-    const bool w = cfg_.log_workers, sv = cfg_.log_server && lane == log_lane_;
-    const int n = (w ? 1 : 0) + (sv ? 1 : 0);
-    if (n) {
-      int sl[2];
-      uint64_t sq[2];
-      uintptr_t ad[2];
-      check(api().sink_acquire_many(reinterpret_cast<void*>(cfg_.sink), n, sl, sq, ad), "metrics sink acquire");
-      int i = 0;
-      if (w) {
-        rr.slot_w = sl[i];
-        rr.seq_w = sq[i];
-        q.slot_w = ad[i];
-        q.seq_w = (unsigned)sq[i];
-        ++i;
-      }
-      if (sv) {
-        rr.slot_s = sl[i];
-        rr.seq_s = sq[i];
-        q.slot_s = ad[i];
-        q.seq_s = (unsigned)sq[i];
-      }
-    }
-  }
-  q.delay_us = lane < (int)cfg_.delay_us.size() ? cfg_.delay_us[lane] : 0;
-  q.pull_tag = peer_rx_ ? pull_tag_[lane] : 0u;
-  write_release(lane, q);
-  return true;
+AsyncToken LanesLoop::read_token(uint64_t n) {
+  const volatile AsyncToken* slot = tok_host_ + (n % (uint64_t)ring_);
+  __m128i v = _mm_load_si128((const __m128i*)(const void*)slot);
+  AsyncToken tk;
+  std::memcpy(&tk, &v, 16);
+  if (tk.tag == (unsigned)n) std::atomic_thread_fence(std::memory_order_acquire);
+  return tk;
 }
 
 void LanesLoop::set_trace(int cap) {
@@ -1262,7 +1123,7 @@ void LanesLoop::set_trace(int cap) {
   }
   tr_cap_ = cap > 0 ? cap : 0;
   tr_n_ = tr_taken_ = 0;
-  tr_tick_ = aticket_;
+  tr_tick_ = proto_.tickets();
   if (!tr_cap_) return;
   const size_t bytes = ((size_t)tr_cap_ * kMaxLanes * 4 + 2 * kMaxLanes) * sizeof(long long);
   hip_check(hipMalloc((void**)&tr_, bytes), "trace ring");
@@ -1289,13 +1150,14 @@ std::vector<std::vector<int64_t>> LanesLoop::trace_take(hipStream_t s) {
   }
   tr_taken_ = tr_n_;
   // asynchronous tickets (their entries are [t % cap][4] in the same ring)
-  const uint64_t t0 = std::max<uint64_t>(tr_tick_, aticket_ > (uint64_t)tr_cap_ ? aticket_ - tr_cap_ : 0);
-  for (uint64_t t = t0 + 1; t <= aticket_; ++t) {
+  const uint64_t aticket = proto_.tickets();
+  const uint64_t t0 = std::max<uint64_t>(tr_tick_, aticket > (uint64_t)tr_cap_ ? aticket - tr_cap_ : 0);
+  for (uint64_t t = t0 + 1; t <= aticket; ++t) {
     const long long* e = h.data() + (size_t)(t % (uint64_t)tr_cap_) * 4;
     const int l = (int)e[0];
     out.push_back({1, (int64_t)t, l, (l >= 0 && l < L) ? cfg_.k[l] : -1, e[1], e[2], e[3], 0});
   }
-  tr_tick_ = aticket_;
+  tr_tick_ = aticket;
   return out;
 }
 
@@ -1313,7 +1175,7 @@ std::vector<int64_t> LanesLoop::clock_ref(hipStream_t s) {
   return {(int64_t)a.tv_sec * 1000000000ll + a.tv_nsec, ticks, (int64_t)b.tv_sec * 1000000000ll + b.tv_nsec};
 }
 
-std::string LanesLoop::launch_report() {
+std::string LanesLoop::progress_report() {
   // (failure reports) how far the current persistent launch got: its workgroups that
   // claimed a lane slot per XCD and all that started, read on a stream of its own
   // with a bounded wait
@@ -1355,23 +1217,11 @@ void LanesLoop::prepare_async() {
 void LanesLoop::set_injection(const std::vector<int64_t>& crash, const std::vector<int64_t>& stop, bool drop) {
   if ((!crash.empty() && (int)crash.size() != cfg_.L) || (!stop.empty() && (int)stop.size() != cfg_.L))
     throw std::invalid_argument("LanesLoop::set_injection: one entry per lane");
-  inj_crash_ = crash;
-  inj_stop_ = stop;
-  inj_drop_ = drop;
-}
-
-void LanesLoop::stop_lane(int l) {
-  if (lane_stopped_.size() != (size_t)cfg_.L) lane_stopped_.assign(cfg_.L, 0);
-  if (lane_stopped_[l]) return;  // (an unread second stop record would end the lane's next launch at once)
-  RelRec q;
-  std::memset(&q, 0, sizeof(q));
-  q.stop = 1;
-  write_release(l, q);
-  lane_stopped_[l] = 1;
+  proto_.set_injection(crash, stop, drop);
 }
 
 void LanesLoop::stop_all(hipStream_t stream) {
-  for (int l = 0; l < cfg_.L; ++l) stop_lane(l);
+  proto_.stop_lanes();
   // the launch drains once every workgroup has been dispatched and returned; a bounded
   // wait turns a launch that cannot drain into an error that says how far dispatch got
   const double t0 = epoch_ms();
@@ -1394,11 +1244,11 @@ void LanesLoop::stop_all(hipStream_t stream) {
 }
 
 void LanesLoop::launch_async(hipStream_t stream, bool remote) {
-  // local: the snapshot of the current weights (aticket_) + the slices' turn words;
+  // local: the snapshot of the current weights (the last ticket) + the slices' turn words;
   // remote: the ticket (= this rank's push order) only
   AsyncArgs a = aargs_;
   a.lr = cfg_.lr;  // the server step (ServerProcessor.java:36): w += lr * delta
-  a.log_lane = remote ? -1 : log_lane_;
+  a.log_lane = remote ? -1 : proto_.log_lane();
   a.remote = remote ? 1 : 0;
   a.xcd0 = cfg_.xcd0;
   if (remote) a.w = nullptr;
@@ -1408,18 +1258,18 @@ void LanesLoop::launch_async(hipStream_t stream, bool remote) {
   a.dbg_cap = dbg_cap_ > 0 ? dbg_cap_ : 1;
   a.launch = ++launch_no_;
   a.cpar = (int)(launches_ & 1);
-  lane_stopped_.assign(cfg_.L, 0);
+  proto_.on_launch();
   // the lanes' release / pull waits outlast the host loop's own no-progress limit
-  a.rel_ticks = (long long)((std::min(rel_wait_s_, 7200.0) + 10.0) * 1e8);
+  a.rel_ticks = (long long)((std::min(proto_.rel_wait_s(), 7200.0) + 10.0) * 1e8);
   hip_check(hipEventRecord(aev_in_, stream), "async order in");  // after the caller's work so far
   hip_check(hipStreamWaitEvent(astream_, aev_in_, 0), "async order in");
   if (remote) {
     // nothing to initialise: the device ticket counter only ever counts this loop's
-    // pushes, so it equals aticket_ (every push is consumed before a run ends).  No copy
+    // pushes, so it equals the last ticket (every push is consumed before a run ends).  No copy
     // or fill before a remote launch: on a GPU shared with other ranks' persistent
     // launches the runtime's copy / fill work waits behind them (profiles/r05/README.md)
   } else {
-    launch_async_init(cfg_.scfg, a, aticket_, astream_);
+    launch_async_init(cfg_.scfg, a, proto_.tickets(), astream_);
     hip_check(hipGetLastError(), "async init launch");
   }
   AsyncPack pk;
@@ -1437,177 +1287,16 @@ int64_t LanesLoop::run_async(int64_t updates, hipStream_t stream, double max_wai
   return run_async(updates, stream, max_wait_s, deadline_ms, b);
 }
 
-int64_t LanesLoop::run_async(int64_t updates, hipStream_t stream, double max_wait_s, double deadline_ms,
-                             const std::vector<int64_t>& lane_budget) {
-  const int64_t t_begin = steady_ns();
-  if (!lane_budget.empty() && (int)lane_budget.size() != cfg_.L)
-    throw std::invalid_argument("LanesLoop::run_async: one budget per lane");
-  auto at_budget = [&](int l, int64_t started) { return !lane_budget.empty() && started >= lane_budget[l]; };
-  if (!cfg_.tracker) throw std::invalid_argument("LanesLoop::run_async: needs the tracker");
-  ensure_async();
-  const int L = cfg_.L;
-  void* trk = reinterpret_cast<void*>(cfg_.tracker);
-  log_lane_ = (cfg_.log_worker >= 0 && cfg_.log_worker < cfg_.N) ? lane_of_[cfg_.log_worker] : -1;
-  // where this run starts: the lanes the tracker has dispatched (bootstrap: all, vc
-  // 0, MessageTracker.java:47-53), the others wait for a release
-  for (int l = 0; l < L; ++l) {
-    // a worker the tracker retired (it crashed or left in an earlier call: its `sent` bit
-    // stays set) never starts again -- its lane stays gone and gets a stop record below
-    const int live = api().tracker_is_live(trk, cfg_.k[l]);
-    check(live, "tracker state");
-    const int sent = api().tracker_is_sent(trk, cfg_.k[l]);
-    check(sent, "tracker state");
-    state_[l] = !live ? kGone : (sent ? kWant : kIdle);
-    want_vc_[l] = api().tracker_clock(trk, cfg_.k[l]);
-    check(want_vc_[l], "tracker clock");
-  }
-  // the lanes' release waits (the device) and the row-starved waits below are idle waits:
-  // bounded by the idle limit, not by the in-flight watchdog max_wait_s
-  rel_wait_s_ = std::max(max_wait_s, idle_wait_s_);
-  // fault injection of this run (set_injection), consumed here
-  const std::vector<int64_t> crash = std::move(inj_crash_), stop = std::move(inj_stop_);
-  inj_crash_.clear();
-  inj_stop_.clear();
-  crashed_.clear();
-  left_.clear();
-  launch_async(stream, false);
-  int64_t started = 0, done = 0;
-  std::vector<int64_t> lane_started((size_t)L, 0);
-  int running = 0;
-  bool stopping = updates <= 0;
-  std::vector<int> ks((size_t)cfg_.N);
-  std::vector<int64_t> vs((size_t)cfg_.N);
-  // the first n entries of the tracker's release list (ks, vs): those workers' lanes want
-  // the weights of that clock
-  auto want_released = [&](int n) {
-    for (int i = 0; i < n; ++i) {
-      const int j = ks[i] >= 0 && ks[i] < cfg_.N ? lane_of_[ks[i]] : -1;
-      if (j < 0) throw std::logic_error("LanesLoop: the tracker released a worker this loop does not host");
-      if (state_[j] == kGone) continue;
-      state_[j] = kWant;
-      want_vc_[j] = vs[i];
-    }
-  };
-  // a lane whose worker crashed / left: it gets its stop record now (its workgroups
-  // leave the launch), the tracker retires the worker (the others are no longer held
-  // back by its clock) and the lanes that releases are dispatched
-  auto lane_leave = [&](int l, bool crashed) {
-    const int k = cfg_.k[l];
-    state_[l] = kGone;
-    stop_lane(l);
-    (crashed ? crashed_ : left_).push_back(k);
-    if (crashed && !inj_drop_) {  // --on_worker_failure fail: the run ends here
-      stopping = true;
-      return;
-    }
-    if (l == log_lane_) {  // server rows follow the lowest surviving worker's deltas
-      int nl = -1;
-      for (int j = 0; j < L; ++j)
-        if (state_[j] != kGone && (nl < 0 || cfg_.k[j] < cfg_.k[nl])) nl = j;
-      log_lane_ = nl;
-      if (nl >= 0) cfg_.log_worker = cfg_.k[nl];
-    }
-    const int n = api().tracker_retire(trk, k, ks.data(), vs.data(), cfg_.N);
-    check(n, "tracker retire");
-    want_released(n);
-  };
+// Launch, run `loop` (the protocol's), drain.  Never leave the persistent launch running
+// behind an exception.
+template <class Loop>
+int64_t LanesLoop::serve_async(hipStream_t stream, bool remote, int64_t t_begin, Loop loop) {
+  launch_async(stream, remote);
+  int64_t done = 0;
   try {
-    auto start_ready = [&](double now) {
-      for (int l = 0; l < L; ++l) {
-        if (state_[l] != kWant || stopping || started >= updates) continue;
-        if (!crash.empty() && crash[l] >= 0 && lane_started[l] >= crash[l]) {
-          lane_leave(l, true);  // released, and fails before its solve (roles.py WorkerRole.compute)
-          l = -1;               // (a retirement may have released a lane already passed)
-          continue;
-        }
-        if (at_budget(l, lane_started[l])) continue;
-        if (try_release(l, want_vc_[l], now)) {
-          state_[l] = kRunning;
-          ++started;
-          ++lane_started[l];
-          ++running;
-        }
-      }
-    };
-    double wait0 = epoch_ms();
-    start_ready(epoch_ms() - cfg_.t0_ms);
-    uint64_t next = aticket_ + 1;
-    int64_t idle_spins = 0;
-    for (;;) {
-      const volatile AsyncToken* slot = tok_host_ + (next % (uint64_t)ring_);
-      __m128i v = _mm_load_si128((const __m128i*)(const void*)slot);
-      AsyncToken tk;
-      std::memcpy(&tk, &v, 16);
-      if (tk.tag == (unsigned)next) {
-        const int64_t tk0 = steady_ns();
-        std::atomic_thread_fence(std::memory_order_acquire);
-        const int l = (int)tk.a;
-        const int64_t vc = (int64_t)(((uint64_t)tk.c << 32) | tk.b);
-        if (l < 0 || l >= L || state_[l] != kRunning || runrec_[l].vc != vc)
-          throw std::logic_error("LanesLoop: unexpected token (lane " + std::to_string(l) + ", vc " +
-                                 std::to_string((long long)vc) + ")");
-        aticket_ = next++;
-        --running;
-        ++done;
-        // the rows of the iteration: server row first (ServerProcessor.java:154-165), then the worker row
-        const RunRec& rr = runrec_[l];
-        if (dbg_delta_)
-          alog_.push_back({(int64_t)aticket_, l, cfg_.k[l], vc, rr.snap, rr.r.B, rr.r.start, rr.r.first, rr.r.step,
-                           rr.r.n, rr.r.first2, rr.r.n2});
-        SinkRecord rec[2];
-        int nr = 0;
-        if (rr.slot_s >= 0) rec[nr++] = SinkRecord{rr.slot_s, 1 | kSinkTagged, rr.seq_s, -1, -1, vc, 0};
-        if (rr.slot_w >= 0) rec[nr++] = SinkRecord{rr.slot_w, kSinkTagged, rr.seq_w, -1, cfg_.k[l], vc, rr.nseen};
-        if (nr) check(api().sink_submit_many(reinterpret_cast<void*>(cfg_.sink), nr, rec), "metrics sink submit");
-        state_[l] = kIdle;
-        const int n = api().tracker_on_delta(trk, cfg_.k[l], vc, ks.data(), vs.data(), cfg_.N);
-        check(n, "tracker");
-        want_released(n);
-        if (!stop.empty() && stop[l] >= 0 && lane_started[l] >= stop[l]) lane_leave(l, false);
-        if (deadline_ms > 0.0 && epoch_ms() >= deadline_ms) stopping = true;
-        start_ready(epoch_ms() - cfg_.t0_ms);
-        idle_spins = 0;
-        wait0 = epoch_ms();
-        ++tok_n_;
-        tok_ns_ += (double)(steady_ns() - tk0);
-        continue;
-      }
-      if (running > 0) {  // solves in flight: spin for their tokens
-        if ((++idle_spins & 1023) == 0) {
-          check_errors(-1);
-          const double now = epoch_ms();
-          if (deadline_ms > 0.0 && now >= deadline_ms) stopping = true;
-          if (now - wait0 > max_wait_s * 1000.0)
-            throw std::runtime_error("LanesLoop: no delta from the device for " + std::to_string(max_wait_s) + " s");
-        } else {
-          _mm_pause();
-        }
-        continue;
-      }
-      // nothing in flight: is the run over?
-      if (stopping || started >= updates) break;
-      bool any_want = false, end = false;
-      for (int l = 0; l < L; ++l)
-        if (state_[l] == kWant && !at_budget(l, lane_started[l])) {
-          int64_t size = 0, start = 0, sn = 0;
-          check(api().window_state(reinterpret_cast<void*>(cfg_.window[l]), &size, &start, &sn), "window state");
-          if (size <= 0 && exhausted(l)) end = true;  // a worker with no rows left: the run ends
-          any_want = true;
-        }
-      if (end || !any_want) break;
-      const double now = epoch_ms();
-      if (deadline_ms > 0.0 && now >= deadline_ms) break;
-      start_ready(now - cfg_.t0_ms);  // every dispatched lane waits for rows (producer clock / cadence)
-      if (running == 0) {
-        if (now - wait0 > idle_wait_s_ * 1000.0) throw std::runtime_error("LanesLoop: no rows for a worker");
-        std::this_thread::sleep_for(std::chrono::microseconds(200));
-      } else {
-        wait0 = epoch_ms();
-      }
-    }
+    done = loop();
     stop_all(stream);
   } catch (...) {
-    // never leave the persistent launch running behind an exception
     try {
       stop_all(stream);
     } catch (...) {
@@ -1616,9 +1305,20 @@ int64_t LanesLoop::run_async(int64_t updates, hipStream_t stream, double max_wai
   }
   check_errors(-1);
   last_par_ = 0;  // the lanes wrote loss / fragments of buffer 0
-  async_updates_ += done;
-  async_ns_ += (double)(steady_ns() - t_begin);
+  proto_.account(done, (double)(steady_ns() - t_begin));
   return done;
+}
+
+int64_t LanesLoop::run_async(int64_t updates, hipStream_t stream, double max_wait_s, double deadline_ms,
+                             const std::vector<int64_t>& lane_budget) {
+  const int64_t t_begin = steady_ns();
+  if (!lane_budget.empty() && (int)lane_budget.size() != cfg_.L)
+    throw std::invalid_argument("LanesLoop::run_async: one budget per lane");
+  if (!cfg_.tracker) throw std::invalid_argument("LanesLoop::run_async: needs the tracker");
+  ensure_async();
+  proto_.begin_local(max_wait_s);
+  return serve_async(stream, false, t_begin,
+                     [&] { return proto_.run_local(updates, max_wait_s, deadline_ms, lane_budget); });
 }
 
 void LanesLoop::set_peer(uintptr_t rx_data, uintptr_t rx_tags, int64_t rx_stride, const std::vector<uintptr_t>& inbox,
@@ -1634,7 +1334,6 @@ void LanesLoop::set_peer(uintptr_t rx_data, uintptr_t rx_tags, int64_t rx_stride
   peer_stride_ = rx_stride;
   peer_inbox_ = inbox;
   peer_inbox_tag_ = inbox_tag;
-  pull_tag_.assign(L, 0u);
 }
 
 int64_t LanesLoop::run_async_remote(P2P* p2p, uintptr_t ctrl, uintptr_t reply, int64_t iters, hipStream_t stream,
@@ -1652,126 +1351,25 @@ int64_t LanesLoop::run_async_remote(P2P* p2p, uintptr_t ctrl, uintptr_t reply, i
     pull_ev_.assign(L, nullptr);
     for (auto& e : pull_ev_) hip_check(hipEventCreateWithFlags(&e, hipEventDisableTiming), "hipEventCreate");
   }
-  enum { kWaitPull = 3, kPulling = 4, kDone = 5 };
-  for (int l = 0; l < L; ++l) state_[l] = kWaitPull;  // the server's begin() sends everybody its clock
-  std::vector<int64_t> it(L, 0);
-  rel_wait_s_ = std::max(max_wait_s, idle_wait_s_);
-  launch_async(stream, true);
-  int64_t done = 0;
-  int running = 0, finished = 0;
-  void* rq = reinterpret_cast<void*>(reply);
-  void* cq = reinterpret_cast<void*>(ctrl);
-  auto window_empty = [&](int l) {
-    int64_t size = 0, start = 0, sn = 0;
-    check(api().window_state(reinterpret_cast<void*>(cfg_.window[l]), &size, &start, &sn), "window state");
-    return size <= 0;
-  };
-  try {
-    double wait0 = epoch_ms();
-    uint64_t next = aticket_ + 1;
-    int64_t spins = 0;
-    while (finished < L || running > 0) {
-      bool progress = false;
-      // the server's releases, in its send order to this rank
-      CtrlToken rt{};
-      while (api().ctrl_pop(rq, &rt, 0.0) == 1) {
-        const int j = rt.worker >= 0 && rt.worker < cfg_.N ? lane_of_[rt.worker] : -1;
-        if (j < 0 || state_[j] != kWaitPull)
-          throw std::logic_error("LanesLoop: reply for worker " + std::to_string(rt.worker) + " not waiting");
-        want_vc_[j] = rt.vc;
-        progress = true;
-        if (peer) {  // the server GPU writes the weights into slot j itself: the lane waits for tag aux
-          pull_tag_[j] = (unsigned)rt.aux;
-          state_[j] = kWant;
-          continue;
-        }
-        p2p->recv(aargs_.snap + (size_t)j * P_, (size_t)P_, Comm::kF32, 0, cs);
-        hip_check(hipEventRecord(pull_ev_[j], cs), "pull event");
-        state_[j] = kPulling;
-      }
-      const double now = epoch_ms();
-      for (int l = 0; l < L; ++l) {
-        if (state_[l] == kPulling) {
-          const hipError_t q = hipEventQuery(pull_ev_[l]);
-          if (q == hipSuccess)
-            state_[l] = kWant;
-          else if (q != hipErrorNotReady)
-            hip_check(q, "pull event query");
-        }
-        if (state_[l] == kWant && try_release(l, want_vc_[l], now - cfg_.t0_ms, l)) {
-          state_[l] = kRunning;
-          ++running;
-          progress = true;
-        }
-      }
-      // the lanes' pushes, in their push (ticket) order
-      const volatile AsyncToken* slot = tok_host_ + (next % (uint64_t)ring_);
-      __m128i v = _mm_load_si128((const __m128i*)(const void*)slot);
-      AsyncToken tk;
-      std::memcpy(&tk, &v, 16);
-      if (tk.tag == (unsigned)next) {
-        std::atomic_thread_fence(std::memory_order_acquire);
-        const int l = (int)tk.a;
-        const int64_t vc = (int64_t)(((uint64_t)tk.c << 32) | tk.b);
-        if (l < 0 || l >= L || state_[l] != kRunning || runrec_[l].vc != vc)
-          throw std::logic_error("LanesLoop: unexpected token (lane " + std::to_string(l) + ")");
-        aticket_ = next++;
-        --running;
-        ++done;
-        const bool fin = ++it[l] >= iters || (deadline_ms > 0.0 && now >= deadline_ms) ||
-                         (exhausted(l) && window_empty(l));
-        // push: the delta to the server, then its token (WorkerTrainingProcessor.java:95-97);
-        // peer data plane: the lane already wrote it into the server's inbox (tagged)
-        if (!peer) p2p->send(lanes_[l].dv.delta, (size_t)P_, Comm::kF32, 0, cs);
-        CtrlToken ct{};
-        ct.worker = cfg_.k[l];
-        ct.kind = fin ? 1 : 0;
-        ct.vc = vc;
-        ct.aux = runrec_[l].nseen;
-        if (api().ctrl_push(cq, &ct, max_wait_s) != 1) throw std::runtime_error("LanesLoop: control queue full");
-        const RunRec& rr = runrec_[l];
-        if (rr.slot_w >= 0) {
-          SinkRecord rec{rr.slot_w, kSinkTagged, rr.seq_w, -1, cfg_.k[l], vc, rr.nseen};
-          check(api().sink_submit_many(reinterpret_cast<void*>(cfg_.sink), 1, &rec), "metrics sink submit");
-        }
-        state_[l] = fin ? (int)kDone : (int)kWaitPull;
-        finished += fin ? 1 : 0;
-        progress = true;
-      }
-      if (progress) {
-        wait0 = epoch_ms();
-        spins = 0;
-        continue;
-      }
-      if ((++spins & 1023) == 0) {
-        check_errors(-1);
-        if (epoch_ms() - wait0 > max_wait_s * 1000.0) {
-          std::string m = "LanesLoop: no progress with the server for " + std::to_string(max_wait_s) +
-                          " s; lanes (state 1 want / 2 running / 3 wait pull / 4 pulling / 5 done, vc, pull tag):";
-          for (int l = 0; l < L; ++l)
-            m += " [" + std::to_string(state_[l]) + " " + std::to_string((long long)want_vc_[l]) + " " +
-                 std::to_string(peer ? pull_tag_[l] : 0u) + " it " + std::to_string((long long)it[l]) + "]";
-          m += "; tokens pushed " + std::to_string((long long)done) + "; " + launch_report();
-          throw std::runtime_error(m);
-        }
-        if (running == 0) std::this_thread::sleep_for(std::chrono::microseconds(100));
-      } else {
-        _mm_pause();
-      }
-    }
-    stop_all(stream);
-  } catch (...) {
-    try {
-      stop_all(stream);
-    } catch (...) {
-    }
-    throw;
-  }
-  check_errors(-1);
-  last_par_ = 0;
-  async_updates_ += done;
-  async_ns_ += (double)(steady_ns() - t_begin);
-  return done;
+  rp2p_ = p2p;
+  rcs_ = cs;
+  proto_.begin_remote(max_wait_s);
+  return serve_async(stream, true, t_begin,
+                     [&] { return proto_.run_remote(peer, ctrl, reply, iters, max_wait_s, deadline_ms); });
 }
+
+// the host transport of run_async_remote: the server's weights into lane l's receive slot
+void LanesLoop::begin_pull(int lane) {
+  rp2p_->recv(aargs_.snap + (size_t)lane * P_, (size_t)P_, Comm::kF32, 0, rcs_);
+  hip_check(hipEventRecord(pull_ev_[lane], rcs_), "pull event");
+}
+
+bool LanesLoop::pull_done(int lane) {
+  const hipError_t q = hipEventQuery(pull_ev_[lane]);
+  if (q != hipSuccess && q != hipErrorNotReady) hip_check(q, "pull event query");
+  return q == hipSuccess;
+}
+
+void LanesLoop::send_delta(int lane) { rp2p_->send(lanes_[lane].dv.delta, (size_t)P_, Comm::kF32, 0, rcs_); }
 
 }  // namespace psx

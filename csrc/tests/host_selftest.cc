@@ -10,7 +10,10 @@
 //   tracker fault handling (retire / bsp_round),
 //   libsvm_save / libsvm_load round trip (multithreaded mmap parser),
 //   ServerProtocol (the SSP / ASP server loop of AsyncServer and PeerServer) over a
-//   real tracker and token queue with a scripted data plane.
+//   real tracker and token queue with a scripted data plane,
+//   AsyncLanesProtocol (the host logic of LanesLoop::run_async / run_async_remote) over
+//   a real tracker, real windows, a real metrics sink and real token queues with a
+//   scripted plane (release records, tokens) and a scripted clock.
 // Exit status 0 = all checks passed.
 #include <atomic>
 #include <chrono>
@@ -18,6 +21,8 @@
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
+#include <deque>
+#include <memory>
 #include <string>
 #include <thread>
 #include <unistd.h>
@@ -25,6 +30,7 @@
 
 #include "../host/ctrl.h"
 #include "../host/dataset.h"
+#include "../host/lanes_protocol.h"
 #include "../host/libsvm.h"
 #include "../host/logger.h"
 #include "../host/metrics_sink.h"
@@ -555,6 +561,663 @@ static void test_server_protocol() {
   q.unlink();
 }
 
+// ---- AsyncLanesProtocol -------------------------------------------------------
+// Everything the protocol does to its plane, the tracker, the sink and the control
+// queue, in order, as one line of words:
+//   r(lane,tag,vc,snap,B,start,n,dst,first,step,first2,n2,w,s,pull)   a release record
+//        (w / s: 1 = a worker-row / server-row slot was acquired)     x(lane,tag)  a stop record
+//   dK@V / rK    tracker on_delta / retire (as above)
+//   m[..]        rows handed to the sink, in order: s@vc server row, wK@vc:seen worker row
+//   c[k,kind,vc,aux]   control token pushed (remote)
+//   bpL / pdL / sdL    begin-pull, pull landed, send-delta of lane L (remote, host transport)
+// The expected lines are what LanesLoop::run_async / run_async_remote, poll_async and
+// try_release did before they became this class, written out by hand.  The standard rig:
+// rows arrive 4 per release attempt (per_iter_rows), the windows hold at most 8 rows in a
+// ring of 16 (their target stays at the maximum), the ring of a lane has 16 slots.
+static std::string rel_word(int l, unsigned tag, long long vc, long long snap, int B, int start, int n, int dst,
+                            long long first, long long step, long long first2, int n2, int w, int s, unsigned pull) {
+  const long long v[] = {l, tag, vc, snap, B, start, n, dst, first, step, first2, n2, w, s, pull};
+  std::string o = "r(";
+  for (size_t i = 0; i < sizeof(v) / sizeof(v[0]); ++i) o += (i ? "," : "") + std::to_string(v[i]);
+  return o + ")";
+}
+#define R rel_word
+
+class LanesRig;
+static LanesRig* g_rig = nullptr;
+static int lanes_traced_submit(void* sink, int n, const SinkRecord* recs) {
+  std::string w = "m[";
+  for (int i = 0; i < n; ++i) {
+    w += i ? "," : "";
+    if (recs[i].kind & 1)
+      w += "s@" + std::to_string((long long)recs[i].vc);
+    else
+      w += "w" + at((int)recs[i].partition, recs[i].vc) + ":" + std::to_string((long long)recs[i].nseen);
+  }
+  say(w + "]");
+  return host_api()->sink_submit_many(sink, n, recs);
+}
+static int lanes_traced_push(void* q, const CtrlToken* t, double timeout_s);
+static const HostApi* lanes_api() {
+  static HostApi a = [] {
+    HostApi x = *host_api();
+    x.tracker_on_delta = traced_on_delta;
+    x.tracker_retire = traced_retire;
+    x.sink_submit_many = lanes_traced_submit;
+    x.ctrl_push = lanes_traced_push;
+    return x;
+  }();
+  return &a;
+}
+
+struct LanesRigOpt {
+  int N = 3;
+  std::vector<int> k = {0, 1, 2};  // the lanes' workers
+  int c = -1;                      // consistency (ASP)
+  int per_iter_rows = 4;
+  double p_ms = 0.0;
+  int64_t ds_rows = 3000, epochs = 1;
+  bool peer = false;
+};
+
+class LanesRig : public AsyncLanesPlane {
+ public:
+  // a scripted token: lane `lane` pushes (vc < 0: at the clock of its release); the clock
+  // advances by adv_ms first; force: also when the lane has no solve in flight;
+  // empty_window: the lane's window is emptied first
+  struct Tok {
+    int lane;
+    int64_t vc = -1;
+    double adv_ms = 0.0;
+    bool force = false, empty_window = false;
+  };
+  explicit LanesRig(const LanesRigOpt& o = LanesRigOpt())
+      : trk(o.N, o.c), slots_(16),
+        qname_("/psx_selftest_lanes_" + std::to_string(getpid()) + "_" + std::to_string(++rigs_)) {
+    std::memset(slots_.data(), 0, sizeof(EvalSlot) * slots_.size());
+    sink.reset(new MetricsSink(reinterpret_cast<uintptr_t>(slots_.data()), (int)slots_.size(), 2, nullptr, nullptr,
+                               true));
+    ctrl.reset(new CtrlQueue(qname_ + "_c", 64, true));
+    reply.reset(new CtrlQueue(qname_ + "_r", 64, true));
+    const int L = (int)o.k.size();
+    cfg.N = o.N;
+    cfg.L = L;
+    cfg.k = o.k;
+    cfg.per_iter_rows = o.per_iter_rows;
+    cfg.p_ms = o.p_ms;
+    cfg.ds_rows = o.ds_rows;
+    cfg.epochs = o.epochs;
+    cfg.sink = reinterpret_cast<uintptr_t>(sink.get());
+    cfg.tracker = reinterpret_cast<uintptr_t>(&trk);
+    cfg.api = reinterpret_cast<uintptr_t>(lanes_api());
+    for (int l = 0; l < L; ++l) {
+      win.emplace_back(new SlidingWindow(1, 8, 100.0, 500, 16));
+      cfg.window.push_back(reinterpret_cast<uintptr_t>(win.back().get()));
+      local_total.push_back(o.ds_rows > o.k[l] ? (o.ds_rows - o.k[l] + o.N - 1) / o.N : 0);
+    }
+    next_local.assign(L, 0);
+    seen_at_solve.assign(L, 0);
+    last_.assign(L, RelRec{});
+    inflight_.assign(L, 0);
+    pull_left_.assign(L, 0);
+    p.bind(&cfg, 16, o.peer, this, &local_total, &next_local, &seen_at_solve, &times_);
+    g_trace = &trace_;
+    g_rig = this;
+  }
+  ~LanesRig() override {
+    g_trace = nullptr;
+    g_rig = nullptr;
+    sink->close();
+    ctrl->unlink();
+    reply->unlink();
+  }
+  // one call of LanesLoop::run_async / run_async_remote without the GPU: the launch resets the
+  // stop bookkeeping, the drain gives every lane its stop record -- also behind an exception
+  int64_t local(int64_t updates, double max_wait_s = 0.5, double deadline_ms = 0.0,
+                const std::vector<int64_t>& budget = std::vector<int64_t>()) {
+    p.begin_local(max_wait_s);
+    p.on_launch();
+    return drained([&] { return p.run_local(updates, max_wait_s, deadline_ms, budget); });
+  }
+  int64_t remote(bool peer, int64_t iters, double max_wait_s = 0.5, double deadline_ms = 0.0) {
+    p.begin_remote(max_wait_s);
+    p.on_launch();
+    return drained([&] {
+      return p.run_remote(peer, reinterpret_cast<uintptr_t>(ctrl.get()), reinterpret_cast<uintptr_t>(reply.get()),
+                          iters, max_wait_s, deadline_ms);
+    });
+  }
+  void feed(std::initializer_list<int> lanes) {
+    for (int l : lanes) script.push_back(Tok{l});
+  }
+  void push_reply(int worker, int64_t vc, int64_t aux) {
+    CtrlToken t{};
+    t.worker = worker;
+    t.vc = vc;
+    t.aux = aux;
+    if (!reply->push(t, 10.0)) std::abort();
+  }
+  // the words since the last call; brief: the releases as rL@vc and the stops as xL only
+  std::string take() {
+    std::string out;
+    for (const auto& w : trace_) out += (out.empty() ? "" : " ") + w;
+    trace_.clear();
+    brief_.clear();
+    return out;
+  }
+  std::string take_brief() {
+    const std::string out = brief_;
+    take();
+    return out;
+  }
+
+  LanesHostCfg cfg;
+  AsyncLanesProtocol p;
+  VectorClockTracker trk;
+  std::unique_ptr<MetricsSink> sink;
+  std::unique_ptr<CtrlQueue> ctrl, reply;
+  std::vector<std::unique_ptr<SlidingWindow>> win;
+  std::vector<int64_t> local_total, next_local, seen_at_solve;
+  std::deque<Tok> script;
+  double t_ms = 1000.0;         // the scripted wall clock
+  double idle_step_ms = 1.0;    // ... advances by this on every look at an empty token slot
+  double sleep_step_ms = -1.0;  // ... and by this per idle sleep (< 0: the sleep's length)
+  int sleeps = 0, polls = 0;
+  int pull_delay = 0;           // pull_done answers false this often per pull
+  bool auto_reply = false;      // a pushed delta token is answered like the server would
+
+ protected:
+  void write_release(int lane, const RelRec& q, unsigned tag) override {
+    TagChunk ch[kRelChunks];
+    pack_release(q, tag, ch);
+    RelRec u;
+    std::memset(&u, 0, sizeof(u));
+    unpack_release(ch, u);
+    for (int i = 0; i < kRelChunks; ++i) CHECK(ch[i].tag == tag);
+    CHECK(u.stop == q.stop && u.vc == q.vc && u.snap == q.snap && u.r.B == q.r.B && u.r.first2 == q.r.first2 &&
+          u.slot_w == q.slot_w && u.slot_s == q.slot_s && u.seq_s == q.seq_s && u.pull_tag == q.pull_tag);
+    if (q.stop) {
+      say("x(" + std::to_string(lane) + "," + std::to_string(tag) + ")");
+      brief_ += (brief_.empty() ? "x" : " x") + std::to_string(lane);
+      return;
+    }
+    say(rel_word(lane, tag, q.vc, q.snap, q.r.B, q.r.start, q.r.n, q.r.dst, q.r.first, q.r.step, q.r.first2, q.r.n2,
+                 q.slot_w != 0, q.slot_s != 0, q.pull_tag));
+    brief_ += (brief_.empty() ? "r" : " r") + at(lane, q.vc);
+    last_[lane] = q;
+    inflight_[lane] = 1;
+    // the "device": the rows' slots are complete before the token (tagged chunks, K = 2)
+    publish(q.slot_w, q.seq_w);
+    publish(q.slot_s, q.seq_s);
+  }
+  AsyncToken read_token(uint64_t n) override {
+    if (script.empty() || (!script.front().force && !inflight_[script.front().lane])) {
+      t_ms += idle_step_ms;
+      return AsyncToken{0u, 0u, 0u, 0u};
+    }
+    const Tok t = script.front();
+    script.pop_front();
+    t_ms += t.adv_ms;
+    if (t.empty_window) win[t.lane]->restore(-1, 0, win[t.lane]->tuples_seen());
+    const uint64_t vc = (uint64_t)(t.vc >= 0 ? t.vc : (int64_t)last_[t.lane].vc);
+    inflight_[t.lane] = 0;
+    return AsyncToken{(unsigned)n, (unsigned)t.lane, (unsigned)vc, (unsigned)(vc >> 32)};
+  }
+  void poll_errors() override { ++polls; }
+  std::string progress_report() override { return "launch 1: scripted"; }
+  void begin_pull(int lane) override {
+    say("bp" + std::to_string(lane));
+    pull_left_[lane] = pull_delay;
+  }
+  bool pull_done(int lane) override {
+    if (pull_left_[lane] > 0) {
+      --pull_left_[lane];
+      return false;
+    }
+    say("pd" + std::to_string(lane));
+    return true;
+  }
+  void send_delta(int lane) override { say("sd" + std::to_string(lane)); }
+  double now_ms() override { return t_ms; }
+  int64_t mono_ns() override { return ns_ += 1000; }
+  void idle_sleep(int us) override {
+    ++sleeps;
+    t_ms += sleep_step_ms >= 0.0 ? sleep_step_ms : us / 1000.0;
+  }
+
+ private:
+  template <class F>
+  int64_t drained(F f) {
+    int64_t done = 0;
+    try {
+      done = f();
+    } catch (...) {
+      p.stop_lanes();
+      throw;
+    }
+    p.stop_lanes();
+    return done;
+  }
+  static void publish(unsigned long long addr, unsigned seq) {
+    if (!addr) return;
+    uint32_t* w = reinterpret_cast<uint32_t*>(addr);
+    for (int i = 0; i < 3; ++i) {  // 1 + (K * K + 2) / 3 chunks
+      w[4 * i + 1] = w[4 * i + 2] = w[4 * i + 3] = 0u;
+      w[4 * i] = seq | 0x80000000u;
+    }
+  }
+  std::vector<EvalSlot> slots_;
+  std::string qname_;
+  std::vector<double> times_;
+  std::vector<std::string> trace_;
+  std::string brief_;
+  std::vector<RelRec> last_;
+  std::vector<uint8_t> inflight_;
+  std::vector<int> pull_left_;
+  int64_t ns_ = 0;
+  static int rigs_;  // (queue names: several rigs live at once)
+};
+int LanesRig::rigs_ = 0;
+
+static int lanes_traced_push(void* q, const CtrlToken* t, double timeout_s) {
+  say("c[" + std::to_string(t->worker) + "," + std::to_string(t->kind) + "," + std::to_string((long long)t->vc) +
+      "," + std::to_string((long long)t->aux) + "]");
+  const int rc = host_api()->ctrl_push(q, t, timeout_s);
+  if (g_rig && g_rig->auto_reply && t->kind == kKindDelta)  // the server: the next weights, tagged
+    g_rig->push_reply(t->worker, t->vc + 1, 100 + 10 * t->worker + t->vc + 1);
+  return rc;
+}
+
+template <class E, class F>
+static std::string error_of(F f) {
+  try {
+    f();
+  } catch (const E& e) {
+    return e.what();
+  } catch (const std::exception& e) {
+    return std::string("(another exception) ") + e.what();
+  }
+  return "(none)";
+}
+
+static void test_lanes_protocol() {
+  LanesRigOpt ssp3;  // 3 lanes, workers 0..2, SSP(1)
+  ssp3.c = 1;
+  const LanesRigOpt asp3;  // the same under ASP
+  LanesRigOpt one;         // 1 lane, worker 0 of 1, ASP
+  one.N = 1;
+  one.k = {0};
+  one.ds_rows = 1000;
+  {  // 1. bootstrap, SSP(1), fresh tracker: everybody at clock 0 with the snapshot of the current
+     // ticket; the tokens come in the order 2, 0, 1 and release their senders in that order with
+     // the snapshot of their own ticket; server row first, and on the log lane (worker 0) only;
+     // every release carries the 4 rows delivered for it (rows k, k + 3, ...)
+    LanesRig g(ssp3);
+    g.feed({2, 0, 1, 2, 0, 1});
+    CHECK(g.local(6) == 6);
+    CHECK_TRACE(g, R(0, 1, 0, 0, 4, 0, 4, 0, 0, 3, 0, 0, 1, 1, 0) + " " + R(1, 1, 0, 0, 4, 0, 4, 0, 1, 3, 0, 0, 1, 0, 0) +
+                       " " + R(2, 1, 0, 0, 4, 0, 4, 0, 2, 3, 0, 0, 1, 0, 0) + " m[w2@0:4] d2@0 " +
+                       R(2, 2, 1, 1, 8, 0, 4, 4, 14, 3, 0, 0, 1, 0, 0) + " m[s@0,w0@0:4] d0@0 " +
+                       R(0, 2, 1, 2, 8, 0, 4, 4, 12, 3, 0, 0, 1, 1, 0) + " m[w1@0:4] d1@0 " +
+                       R(1, 2, 1, 3, 8, 0, 4, 4, 13, 3, 0, 0, 1, 0, 0) +
+                       " m[w2@1:8] d2@1 m[s@1,w0@1:8] d0@1 m[w1@1:8] d1@1 x(0,3) x(1,3) x(2,3)");
+    CHECK(g.p.tickets() == 6 && g.p.log_lane() == 0 && g.p.crashed().empty() && g.p.left().empty());
+    CHECK(g.p.host_busy_us_per_token() == 1.0);  // (the scripted steady clock: 1 us per reading)
+    CHECK(g.sink->flush(30.0));
+    const auto srows = g.sink->server_rows();
+    CHECK(srows.size() == 2 && srows[0].vc == 0 && srows[1].vc == 1 && g.sink->worker_rows().size() == 6);
+  }
+  {  // 2. the SSP gap: worker 1's token is withheld; workers 0 and 2 stop one clock ahead (their
+     // second delta releases nobody) and resume, with worker 1, when it arrives; `updates` = 7
+     // leaves lane 2's release for the next call
+    LanesRig g(ssp3);
+    g.feed({0, 2, 0, 2, 1, 0, 1});
+    CHECK(g.local(7) == 7);
+    CHECK_TRACE(g, R(0, 1, 0, 0, 4, 0, 4, 0, 0, 3, 0, 0, 1, 1, 0) + " " + R(1, 1, 0, 0, 4, 0, 4, 0, 1, 3, 0, 0, 1, 0, 0) +
+                       " " + R(2, 1, 0, 0, 4, 0, 4, 0, 2, 3, 0, 0, 1, 0, 0) + " m[s@0,w0@0:4] d0@0 " +
+                       R(0, 2, 1, 1, 8, 0, 4, 4, 12, 3, 0, 0, 1, 1, 0) + " m[w2@0:4] d2@0 " +
+                       R(2, 2, 1, 2, 8, 0, 4, 4, 14, 3, 0, 0, 1, 0, 0) +
+                       " m[s@1,w0@1:8] d0@1 m[w2@1:8] d2@1 m[w1@0:4] d1@0 " +
+                       R(0, 3, 2, 5, 8, 4, 4, 8, 24, 3, 0, 0, 1, 1, 0) + " " +
+                       R(1, 2, 1, 5, 8, 0, 4, 4, 13, 3, 0, 0, 1, 0, 0) +
+                       " m[s@2,w0@2:12] d0@2 m[w1@1:8] d1@1 x(0,4) x(1,3) x(2,3)");
+    CHECK(g.p.state(2) == AsyncLanesProtocol::kWant && g.trk.is_sent(2) && g.trk.clock(2) == 2);
+  }
+  {  // 3. ASP: a delta releases its sender and nobody else
+    LanesRig g(asp3);
+    g.feed({1, 1, 0, 1, 2});
+    CHECK(g.local(5) == 5);
+    CHECK_TRACE(g, R(0, 1, 0, 0, 4, 0, 4, 0, 0, 3, 0, 0, 1, 1, 0) + " " + R(1, 1, 0, 0, 4, 0, 4, 0, 1, 3, 0, 0, 1, 0, 0) +
+                       " " + R(2, 1, 0, 0, 4, 0, 4, 0, 2, 3, 0, 0, 1, 0, 0) + " m[w1@0:4] d1@0 " +
+                       R(1, 2, 1, 1, 8, 0, 4, 4, 13, 3, 0, 0, 1, 0, 0) + " m[w1@1:8] d1@1 " +
+                       R(1, 3, 2, 2, 8, 4, 4, 8, 25, 3, 0, 0, 1, 0, 0) +
+                       " m[s@0,w0@0:4] d0@0 m[w1@2:12] d1@2 m[w2@0:4] d2@0 x(0,2) x(1,4) x(2,2)");
+  }
+  {  // 4. token validation: a token of a lane without a solve in flight, a token at another
+     // clock than the lane's release; every lane has exactly one stop record afterwards
+    LanesRig g(asp3);
+    LanesRig::Tok idle{1};
+    idle.force = true;
+    g.script.push_back(idle);
+    CHECK(error_of<std::logic_error>([&] { g.local(1); }) == "LanesLoop: unexpected token (lane 1, vc 0)");
+    CHECK_TRACE(g, R(0, 1, 0, 0, 4, 0, 4, 0, 0, 3, 0, 0, 1, 1, 0) + " x(0,2) x(1,1) x(2,1)");
+    LanesRig h(asp3);
+    LanesRig::Tok wrong{0};
+    wrong.vc = 5;
+    h.script.push_back(wrong);
+    CHECK(error_of<std::logic_error>([&] { h.local(3); }) == "LanesLoop: unexpected token (lane 0, vc 5)");
+    CHECK(h.take_brief() == "r0@0 r1@0 r2@0 x0 x1 x2");
+    CHECK(h.p.tickets() == 0);
+  }
+  {  // 5. budgets under ASP: per lane {2, 1, 3} -- no lane starts more than its share, the run
+     // ends when every wanting lane is at its budget; the scalar form (2 each) with updates = 5:
+     // reached exactly
+    LanesRig g(asp3);
+    g.feed({0, 0, 1, 2, 2, 2});
+    CHECK(g.local(100, 0.5, 0.0, {2, 1, 3}) == 6);
+    CHECK(g.take_brief() == "r0@0 r1@0 r2@0 r0@1 r2@1 r2@2 x0 x1 x2");
+    LanesRig h(asp3);
+    h.feed({0, 0, 1, 2, 1});
+    CHECK(h.local(5, 0.5, 0.0, std::vector<int64_t>(3, 2)) == 5);
+    CHECK(h.take_brief() == "r0@0 r1@0 r2@0 r0@1 r1@1 x0 x1 x2");
+  }
+  {  // 6. injected crash, drop policy, SSP(1): lanes 0, 1, 2 host workers 1, 0, 2; worker 0 (lane
+     // 1, the log lane) holds the weights of clock 0, workers 1 and 2 are held at clock 2; lane 1
+     // fails when released: its stop record before any solve, the retirement releases lane 2 and
+     // lane 0 (behind the scan position: the scan restarts), the server rows move to worker 1
+    LanesRigOpt o = ssp3;
+    o.k = {1, 0, 2};
+    LanesRig g(o);
+    g.trk.restore({0, 2, 2}, {1, 0, 0});
+    g.p.set_injection({-1, 0, -1}, {}, true);
+    g.feed({0, 2});
+    CHECK(g.local(2) == 2);
+    CHECK_TRACE(g, "x(1,1) r0 " + R(0, 1, 2, 0, 4, 0, 4, 0, 1, 3, 0, 0, 1, 1, 0) + " " +
+                       R(2, 1, 2, 0, 4, 0, 4, 0, 2, 3, 0, 0, 1, 0, 0) +
+                       " m[s@2,w1@2:4] d1@2 m[w2@2:4] d2@2 x(0,2) x(2,2)");
+    CHECK(g.p.crashed() == std::vector<int>{0} && g.p.left().empty() && !g.trk.is_live(0));
+    CHECK(g.p.log_lane() == 0 && g.cfg.log_worker == 1 && g.p.state(1) == AsyncLanesProtocol::kGone);
+  }
+  {  // 7. injected crash, fail policy: lane 1 fails when released after its first solve; nothing
+     // new starts, the two solves in flight are still consumed, the worker is not retired
+    LanesRig g(asp3);
+    g.p.set_injection({-1, 1, -1}, {}, false);
+    g.feed({1, 0, 2});
+    CHECK(g.local(10) == 3);
+    CHECK_TRACE(g, R(0, 1, 0, 0, 4, 0, 4, 0, 0, 3, 0, 0, 1, 1, 0) + " " + R(1, 1, 0, 0, 4, 0, 4, 0, 1, 3, 0, 0, 1, 0, 0) +
+                       " " + R(2, 1, 0, 0, 4, 0, 4, 0, 2, 3, 0, 0, 1, 0, 0) +
+                       " m[w1@0:4] d1@0 x(1,2) m[s@0,w0@0:4] d0@0 m[w2@0:4] d2@0 x(0,2) x(2,2)");
+    CHECK(g.p.crashed() == std::vector<int>{1} && g.trk.is_live(1) && g.cfg.log_worker == 0);
+  }
+  {  // 8. injected clean leave: lane 0 (the log lane) leaves after 2 solves -- its second delta is
+     // applied and logged, then its stop record and its retirement; the server rows move to
+     // worker 1 with lane 1's next release
+    LanesRig g(asp3);
+    g.p.set_injection({}, {2, -1, -1}, true);
+    g.feed({0, 0, 1, 2, 1});
+    CHECK(g.local(5) == 5);
+    CHECK_TRACE(g, R(0, 1, 0, 0, 4, 0, 4, 0, 0, 3, 0, 0, 1, 1, 0) + " " + R(1, 1, 0, 0, 4, 0, 4, 0, 1, 3, 0, 0, 1, 0, 0) +
+                       " " + R(2, 1, 0, 0, 4, 0, 4, 0, 2, 3, 0, 0, 1, 0, 0) + " m[s@0,w0@0:4] d0@0 " +
+                       R(0, 2, 1, 1, 8, 0, 4, 4, 12, 3, 0, 0, 1, 1, 0) + " m[s@1,w0@1:8] d0@1 x(0,3) r0 m[w1@0:4] d1@0 " +
+                       R(1, 2, 1, 3, 8, 0, 4, 4, 13, 3, 0, 0, 1, 1, 0) +
+                       " m[w2@0:4] d2@0 m[s@1,w1@1:8] d1@1 x(1,3) x(2,2)");
+    CHECK(g.p.left() == std::vector<int>{0} && g.p.crashed().empty() && g.cfg.log_worker == 1);
+    // 9. carry-over into the next call: the retired worker's lane is gone and only gets its stop
+    // record; the releases wanted but not started (1@2, 2@1) start at once; a stop record is
+    // written once per launch, and again in the next launch
+    g.feed({1, 2});
+    CHECK(g.local(2) == 2);
+    CHECK_TRACE(g, R(1, 4, 2, 5, 8, 4, 4, 8, 25, 3, 0, 0, 1, 1, 0) + " " + R(2, 3, 1, 5, 8, 0, 4, 4, 14, 3, 0, 0, 1, 0, 0) +
+                       " m[s@2,w1@2:12] d1@2 m[w2@1:8] d2@1 x(0,4) x(1,5) x(2,4)");
+    CHECK(g.p.left().empty() && g.p.state(0) == AsyncLanesProtocol::kGone && g.p.tickets() == 7);
+    g.p.stop_lanes();
+    CHECK_TRACE(g, "");
+    g.p.on_launch();
+    g.p.stop_lane(1);
+    g.p.stop_lanes();
+    CHECK_TRACE(g, "x(1,6) x(0,5) x(2,5)");
+  }
+  {  // 10a. rows on the producer clock (2 workers, p_ms = 2000: rows 0..255 at 0 ms, row 256 at
+     // 2000 ms, row 257 at 4000 ms): at 0 ms each worker has 128 rows due, the ring keeps the
+     // last 16 (rows 224 + k, step 2), the window its last 8; at 2500 ms worker 0 gets row 256
+     // and worker 1 nothing new (an empty run with the step filled in)
+    LanesRigOpt o;
+    o.N = 2;
+    o.k = {0, 1};
+    o.per_iter_rows = 0;
+    o.p_ms = 2000.0;
+    o.ds_rows = 600;
+    LanesRig g(o);
+    g.t_ms = 0.0;
+    LanesRig::Tok late{0};
+    late.adv_ms = 2500.0;
+    g.script.push_back(late);
+    g.feed({1, 0, 1});
+    CHECK(g.local(4) == 4);
+    CHECK_TRACE(g, R(0, 1, 0, 0, 8, 8, 16, 0, 224, 2, 0, 0, 1, 1, 0) + " " +
+                       R(1, 1, 0, 0, 8, 8, 16, 0, 225, 2, 0, 0, 1, 0, 0) + " m[s@0,w0@0:128] d0@0 " +
+                       R(0, 2, 1, 1, 8, 9, 1, 0, 256, 2, 0, 0, 1, 1, 0) + " m[w1@0:128] d1@0 " +
+                       R(1, 2, 1, 2, 8, 8, 0, 0, 0, 2, 0, 0, 1, 0, 0) +
+                       " m[s@1,w0@1:129] d0@1 m[w1@1:128] d1@1 x(0,3) x(1,3)");
+  }
+  {  // 10b. a delivery across the shard's epoch wrap (18 rows, 2 epochs): the fifth release
+     // carries rows 16, 17 and, as its second run, rows 0, 1
+    LanesRigOpt o = one;
+    o.ds_rows = 18;
+    o.epochs = 2;
+    LanesRig g(o);
+    g.feed({0, 0, 0, 0, 0});
+    CHECK(g.local(5) == 5);
+    CHECK_TRACE(g, R(0, 1, 0, 0, 4, 0, 4, 0, 0, 1, 0, 0, 1, 1, 0) + " m[s@0,w0@0:4] d0@0 " +
+                       R(0, 2, 1, 1, 8, 0, 4, 4, 4, 1, 0, 0, 1, 1, 0) + " m[s@1,w0@1:8] d0@1 " +
+                       R(0, 3, 2, 2, 8, 4, 4, 8, 8, 1, 0, 0, 1, 1, 0) + " m[s@2,w0@2:12] d0@2 " +
+                       R(0, 4, 3, 3, 8, 8, 4, 12, 12, 1, 0, 0, 1, 1, 0) + " m[s@3,w0@3:16] d0@3 " +
+                       R(0, 5, 4, 4, 8, 12, 2, 0, 16, 1, 0, 2, 1, 1, 0) + " m[s@4,w0@4:20] d0@4 x(0,6)");
+  }
+  {  // 10c. the cadence new_rows = 24 holds the lane back for six deliveries (four idle sleeps);
+     // 24 rows are more than the ring's 16: the front 8 are dropped and dst advanced
+    LanesRig g(one);
+    g.cfg.new_rows = 24;
+    g.feed({0});
+    CHECK(g.local(1) == 1);
+    CHECK_TRACE(g, R(0, 1, 0, 0, 8, 0, 16, 8, 8, 1, 0, 0, 1, 1, 0) + " m[s@0,w0@0:24] d0@0 x(0,2)");
+    CHECK(g.sleeps == 4);
+  }
+  {  // 10d. pending rows in a third non-contiguous run (a shard of 6 rows wraps twice)
+    LanesRigOpt o = one;
+    o.ds_rows = 6;
+    o.epochs = 5;
+    LanesRig g(o);
+    g.cfg.new_rows = 100;
+    CHECK(error_of<std::logic_error>([&] { g.local(1); }) == "LanesLoop: pending rows of a release span three runs");
+    CHECK_TRACE(g, "x(0,1)");
+  }
+  {  // 10e. new_frac = 2 (16 new rows for a window of 8): four deliveries; capped by new_cap = 6: two
+    LanesRig g(one);
+    g.cfg.new_frac = 2.0;
+    g.feed({0});
+    CHECK(g.local(1) == 1);
+    CHECK_TRACE(g, R(0, 1, 0, 0, 8, 8, 16, 0, 0, 1, 0, 0, 1, 1, 0) + " m[s@0,w0@0:16] d0@0 x(0,2)");
+    CHECK(g.sleeps == 2);
+    LanesRig h(one);
+    h.cfg.new_frac = 2.0;
+    h.cfg.new_cap = 6;
+    h.feed({0});
+    CHECK(h.local(1) == 1);
+    CHECK_TRACE(h, R(0, 1, 0, 0, 8, 0, 8, 0, 0, 1, 0, 0, 1, 1, 0) + " m[s@0,w0@0:8] d0@0 x(0,2)");
+    CHECK(h.sleeps == 0);
+  }
+  {  // 10f. new_ramp = 4 on top of new_frac = 2: the lane's solves wait for 4, 8, 16 new rows
+     // (one, two, four deliveries)
+    LanesRig g(one);
+    g.cfg.new_frac = 2.0;
+    g.cfg.new_ramp = 4;
+    g.feed({0, 0, 0});
+    CHECK(g.local(3) == 3);
+    CHECK_TRACE(g, R(0, 1, 0, 0, 4, 0, 4, 0, 0, 1, 0, 0, 1, 1, 0) + " m[s@0,w0@0:4] d0@0 " +
+                       R(0, 2, 1, 1, 8, 4, 8, 4, 4, 1, 0, 0, 1, 1, 0) + " m[s@1,w0@1:12] d0@1 " +
+                       R(0, 3, 2, 2, 8, 4, 16, 12, 12, 1, 0, 0, 1, 1, 0) + " m[s@2,w0@2:28] d0@2 x(0,4)");
+    CHECK(g.sleeps == 2);
+  }
+  {  // 10g. an exhausted stream (16 rows, one epoch) releases whatever the cadence asks for: after
+     // the fourth delivery, and again without any new row
+    LanesRigOpt o = one;
+    o.ds_rows = 16;
+    LanesRig g(o);
+    g.cfg.new_rows = 100;
+    g.feed({0, 0});
+    CHECK(g.local(2) == 2);
+    CHECK_TRACE(g, R(0, 1, 0, 0, 8, 8, 16, 0, 0, 1, 0, 0, 1, 1, 0) + " m[s@0,w0@0:16] d0@0 " +
+                       R(0, 2, 1, 1, 8, 8, 0, 0, 0, 1, 0, 0, 1, 1, 0) + " m[s@1,w0@1:16] d0@1 x(0,3)");
+    CHECK(g.sleeps == 2);
+  }
+  {  // 11. watchdogs.  Solves in flight and no token: the scripted clock (1 ms per look at the
+     // empty slot) is past max_wait_s = 0.5 at the first check (every 1,024 looks)
+    LanesRig g(asp3);
+    CHECK(error_of<std::runtime_error>([&] { g.local(3, 0.5); }) ==
+          "LanesLoop: no delta from the device for 0.500000 s");
+    CHECK(g.take_brief() == "r0@0 r1@0 r2@0 x0 x1 x2");
+    CHECK(g.polls == 1 && g.sleeps == 0);
+    // nothing in flight and no rows (the producer clock has not started): the idle limit of 2 s,
+    // not max_wait_s, ends the run -- after 21 sleeps of 100 scripted ms; the lanes' wait budget
+    // on the device is the larger of the two
+    LanesRigOpt o = one;
+    o.per_iter_rows = 0;
+    o.p_ms = 2000.0;
+    LanesRig h(o);
+    h.cfg.t0_ms = 1e9;
+    h.idle_step_ms = 0.0;
+    h.sleep_step_ms = 100.0;
+    h.p.set_idle_wait(2.0);
+    CHECK(error_of<std::runtime_error>([&] { h.local(3, 0.5); }) == "LanesLoop: no rows for a worker");
+    CHECK_TRACE(h, "x(0,1)");
+    CHECK(h.sleeps == 21 && h.p.rel_wait_s() == 2.0);
+    h.p.begin_local(5.0);
+    CHECK(h.p.rel_wait_s() == 5.0);
+  }
+  {  // 12. the deadline (5000 ms; the clock starts at 1000) passes before lane 1's token: nothing
+     // new starts, the solves in flight are consumed, the count is returned
+    LanesRig g(asp3);
+    g.feed({0});
+    LanesRig::Tok late{1};
+    late.adv_ms = 5000.0;
+    g.script.push_back(late);
+    g.feed({2, 0});
+    CHECK(g.local(100, 0.5, 5000.0) == 4);
+    CHECK_TRACE(g, R(0, 1, 0, 0, 4, 0, 4, 0, 0, 3, 0, 0, 1, 1, 0) + " " + R(1, 1, 0, 0, 4, 0, 4, 0, 1, 3, 0, 0, 1, 0, 0) +
+                       " " + R(2, 1, 0, 0, 4, 0, 4, 0, 2, 3, 0, 0, 1, 0, 0) + " m[s@0,w0@0:4] d0@0 " +
+                       R(0, 2, 1, 1, 8, 0, 4, 4, 12, 3, 0, 0, 1, 1, 0) +
+                       " m[w1@0:4] d1@0 m[w2@0:4] d2@0 m[s@1,w0@1:8] d0@1 x(0,3) x(1,2) x(2,2)");
+  }
+  LanesRigOpt rank;  // a worker rank: lanes 0, 1 host workers 2, 3 of 4
+  rank.N = 4;
+  rank.k = {2, 3};
+  rank.ds_rows = 4000;
+  {  // 13. remote over the peer plane, 2 solves per lane: a reply token gives the clock and the pull
+     // tag, the release carries them with snap = the lane; the control token has worker, vc and
+     // aux = tuples seen, FINAL exactly on the second solve; worker rows only; the loop ends when
+     // both lanes are done
+    LanesRigOpt o = rank;
+    o.peer = true;
+    LanesRig g(o);
+    g.auto_reply = true;
+    g.push_reply(2, 0, 7);
+    g.push_reply(3, 0, 9);
+    g.feed({1, 0, 1, 0});
+    CHECK(g.remote(true, 2) == 4);
+    CHECK_TRACE(g, R(0, 1, 0, 0, 4, 0, 4, 0, 2, 4, 0, 0, 1, 0, 7) + " " + R(1, 1, 0, 1, 4, 0, 4, 0, 3, 4, 0, 0, 1, 0, 9) +
+                       " c[3,0,0,4] m[w3@0:4] " + R(1, 2, 1, 1, 8, 0, 4, 4, 19, 4, 0, 0, 1, 0, 131) +
+                       " c[2,0,0,4] m[w2@0:4] " + R(0, 2, 1, 0, 8, 0, 4, 4, 18, 4, 0, 0, 1, 0, 121) +
+                       " c[3,1,1,8] m[w3@1:8] c[2,1,1,8] m[w2@1:8] x(0,3) x(1,3)");
+    CHECK(g.p.state(0) == AsyncLanesProtocol::kDone && g.p.state(1) == AsyncLanesProtocol::kDone);
+    CHECK(g.p.tickets() == 4 && g.ctrl->enqueued() == 4);
+    // a reply for a lane that is not waiting for one
+    LanesRig h(o);
+    h.push_reply(2, 0, 7);
+    h.push_reply(2, 0, 8);
+    CHECK(error_of<std::logic_error>([&] { h.remote(true, 2); }) == "LanesLoop: reply for worker 2 not waiting");
+    CHECK_TRACE(h, "x(0,1) x(1,1)");
+    // FINAL at the deadline (5000 ms): the clock passes it with lane 0's first token, which was
+    // judged at the time read before it; every token after that is FINAL
+    LanesRig d(o);
+    d.auto_reply = true;
+    d.push_reply(2, 0, 7);
+    d.push_reply(3, 0, 9);
+    LanesRig::Tok late{0};
+    late.adv_ms = 5000.0;
+    d.script.push_back(late);
+    d.feed({1, 0});
+    CHECK(d.remote(true, 10, 0.5, 5000.0) == 3);
+    CHECK_TRACE(d, R(0, 1, 0, 0, 4, 0, 4, 0, 2, 4, 0, 0, 1, 0, 7) + " " + R(1, 1, 0, 1, 4, 0, 4, 0, 3, 4, 0, 0, 1, 0, 9) +
+                       " c[2,0,0,4] m[w2@0:4] " + R(0, 2, 1, 0, 8, 0, 4, 4, 18, 4, 0, 0, 1, 0, 121) +
+                       " c[3,1,0,4] m[w3@0:4] c[2,1,1,8] m[w2@1:8] x(0,3) x(1,2)");
+    // FINAL with the stream exhausted (4 rows per worker) and the window empty -- not with rows
+    // still in the window (lane 1's first token)
+    LanesRigOpt e = o;
+    e.ds_rows = 16;
+    LanesRig x(e);
+    x.auto_reply = true;
+    x.push_reply(2, 0, 7);
+    x.push_reply(3, 0, 9);
+    LanesRig::Tok empty0{0}, empty1{1};
+    empty0.empty_window = empty1.empty_window = true;
+    x.script.push_back(empty0);
+    x.feed({1});
+    x.script.push_back(empty1);
+    CHECK(x.remote(true, 10) == 3);
+    CHECK_TRACE(x, R(0, 1, 0, 0, 4, 0, 4, 0, 2, 4, 0, 0, 1, 0, 7) + " " + R(1, 1, 0, 1, 4, 0, 4, 0, 3, 4, 0, 0, 1, 0, 9) +
+                       " c[2,1,0,4] m[w2@0:4] c[3,0,0,4] m[w3@0:4] " +
+                       R(1, 2, 1, 1, 4, 0, 0, 0, 0, 4, 0, 0, 1, 0, 131) + " c[3,1,1,4] m[w3@1:4] x(0,2) x(1,3)");
+  }
+  {  // 14. remote over a host transport: the pulls begin in reply order (worker 3 first), a lane is
+     // released once its pull has landed (the third time it is asked), the delta goes out before
+     // its control token; no pull tags
+    LanesRig g(rank);
+    g.pull_delay = 2;
+    g.push_reply(3, 0, 0);
+    g.push_reply(2, 0, 0);
+    g.feed({1, 0});
+    CHECK(g.remote(false, 1) == 2);
+    CHECK_TRACE(g, "bp1 bp0 pd0 " + R(0, 1, 0, 0, 4, 0, 4, 0, 2, 4, 0, 0, 1, 0, 0) + " pd1 " +
+                       R(1, 1, 0, 1, 4, 0, 4, 0, 3, 4, 0, 0, 1, 0, 0) +
+                       " sd1 c[3,1,0,4] m[w3@0:4] sd0 c[2,1,0,4] m[w2@0:4] x(0,2) x(1,2)");
+    // no progress: lane 0 never hears from the server, lane 1's pull (clock 5) never lands
+    LanesRig h(rank);
+    h.pull_delay = 1 << 30;
+    h.push_reply(3, 5, 0);
+    CHECK(error_of<std::runtime_error>([&] { h.remote(false, 1, 0.5); }) ==
+          "LanesLoop: no progress with the server for 0.500000 s; lanes (state 1 want / 2 running / 3 wait pull / 4 "
+          "pulling / 5 done, vc, pull tag): [3 0 0 it 0] [4 5 0 it 0]; tokens pushed 0; launch 1: scripted");
+    CHECK_TRACE(h, "bp1 x(0,1) x(1,1)");
+    CHECK(h.polls == 1);
+  }
+  {  // 15. the release record's 16-B chunks: 64-bit fields above 2^32, a negative first
+    RelRec q;
+    std::memset(&q, 0, sizeof(q));
+    q.stop = 1;
+    q.vc = (5ll << 32) + 7;
+    q.snap = (9ll << 32) + 1;
+    q.r = LaneRound{1024, 17, 300, 4000, -5, (3ll << 32) + 2, (1ll << 40) + 3, 11, 0};
+    q.slot_w = 0x7f12345678abcdefull;
+    q.slot_s = 0x00007fffdeadbee0ull;
+    q.seq_w = 0xfffffff0u;
+    q.seq_s = 0x80000001u;
+    q.delay_us = 250;
+    q.pull_tag = 0xdeadbeefu;
+    TagChunk ch[kRelChunks];
+    pack_release(q, 0xabcd0123u, ch);
+    RelRec u;
+    std::memset(&u, 0xff, sizeof(u));
+    unpack_release(ch, u);
+    for (int i = 0; i < kRelChunks; ++i) CHECK(ch[i].tag == 0xabcd0123u);
+    CHECK(u.stop == 1 && u.vc == q.vc && u.snap == q.snap && u.r.B == 1024 && u.r.start == 17 && u.r.n == 300 &&
+          u.r.dst == 4000 && u.r.first == -5 && u.r.step == q.r.step && u.r.first2 == q.r.first2 && u.r.n2 == 11 &&
+          u.r.delay_us == 0 && u.slot_w == q.slot_w && u.slot_s == q.slot_s && u.seq_w == q.seq_w &&
+          u.seq_s == q.seq_s && u.delay_us == 250 && u.pull_tag == q.pull_tag);
+  }
+}
+#undef R
+
 int main() {
   test_tracker();
   test_tracker_faults();
@@ -564,6 +1227,7 @@ int main() {
   test_csv();
   test_metrics_sink();
   test_server_protocol();
+  test_lanes_protocol();
   if (g_fail) {
     std::fprintf(stderr, "%d check(s) failed\n", g_fail);
     return 1;
