@@ -574,6 +574,10 @@ PYBIND11_MODULE(_psx_hip, m) {
       py::arg("T"), py::arg("w"), py::arg("table"), py::arg("mask"), py::arg("wloc"), py::arg("acc"),
       py::arg("ticket") = 0, py::arg("slot") = 0, py::arg("loss") = 0, py::arg("seq") = 0, py::arg("stream") = 0,
       py::arg("slot2") = 0, py::arg("seq2") = 0, py::arg("zbase") = 0, py::arg("bias") = 0);
+  // rows per plan group of a ring of NZ-wide rows and KP padded classes (the solve kernels'
+  // launch geometry: block 64 * RB, group EB = RB * NZ); host-only, no device needed
+  m.def("wide_rows_per_group", [](int NZ, int KP) { return wide_rows_per_group(NZ, KP); }, py::arg("NZ"),
+        py::arg("KP"));
   m.def("wide_logits", [](int K, int KP, int64_t F, uintptr_t indptr, uintptr_t idx, uintptr_t val, int T,
                           uintptr_t w, uintptr_t out, uintptr_t stream) {
     launch_wide_logits(K, KP, F, P<const int64_t>(indptr), P<const int32_t>(idx), P<const uint16_t>(val), T,

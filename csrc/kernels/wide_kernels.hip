@@ -263,13 +263,21 @@ __global__ __launch_bounds__(256) void wide_assign_kernel(WideCfg c, WideDev d) 
 }
 
 // stats: local ids of the group's features, every entry's local id, and the
-// feature sums for the 1/std scaling aggregated per group in LDS.
+// feature sums for the 1/std scaling aggregated per group in LDS.  A row's value of
+// a feature is the SUM of its entries (an id may repeat within a row, as in the
+// densified window of the oracle): the moments are of that sum, not of the entries.
+// Entries are summed directly (one pass) unless the group has a row that repeats an
+// id -- seen as the row's bit already set in the feature's row mask -- and then row
+// by row: the row's entries add into the feature's cell, the first to take the cell
+// back accumulates the row's total and its square.
 __device__ __forceinline__ void wide_stats_body(const WideCfg& c, const WideDev& d, int b, int* st_lds) {
   const int EB = d.EB, RB = d.RB, NZ = c.NZ, cap = c.cap;
   const int nthr = blockDim.x;
   int* lid_s = st_lds;                  // [EB]
   float* s1l = (float*)(lid_s + EB);    // [EB]
   float* s2l = s1l + EB;                // [EB]
+  int* rmask = (int*)(s2l + EB);        // [EB] rows (bits) holding the feature; then the row's running sum
+  __shared__ int dup_s;
   const int B = d.prm->B, start = d.prm->start;
   const int t = threadIdx.x;
   const int r0 = b * RB;
@@ -284,7 +292,9 @@ __device__ __forceinline__ void wide_stats_body(const WideCfg& c, const WideDev&
     glid[si] = l;
     s1l[si] = 0.f;
     s2l[si] = 0.f;
+    rmask[si] = 0;
   }
+  if (t == 0) dup_s = 0;
   __syncthreads();
   const int ne = rows * NZ;
   for (int el = t; el < ne; el += nthr) {
@@ -299,9 +309,36 @@ __device__ __forceinline__ void wide_stats_body(const WideCfg& c, const WideDev&
       const float v = bf2f(d.rval[(size_t)sl * NZ + j]);
       atomicAdd(&s1l[ps], v);
       atomicAdd(&s2l[ps], v * v);
+      if (atomicOr(&rmask[ps], 1 << r) & (1 << r)) dup_s = 1;
     }
   }
   __syncthreads();
+  if (c.standardize && dup_s) {  // uniform: a row of this group repeats an id
+    float* rsum = (float*)rmask;
+    for (int si = t; si < n; si += nthr) {
+      s1l[si] = 0.f;
+      s2l[si] = 0.f;
+      rsum[si] = 0.f;
+    }
+    __syncthreads();
+    for (int r = 0; r < rows; ++r) {
+      int sl = start + r0 + r;
+      if (sl >= cap) sl -= cap;
+      const int nnz = d.rnnz[sl];
+      const int64_t e0 = (int64_t)(r0 + r) * NZ;
+      for (int j = t; j < nnz; j += nthr) atomicAdd(&rsum[d.pslot[e0 + j]], bf2f(d.rval[(size_t)sl * NZ + j]));
+      __syncthreads();
+      for (int j = t; j < nnz; j += nthr) {
+        const int ps = d.pslot[e0 + j];
+        const float v = atomicExch(&rsum[ps], 0.f);  // one entry of the row gets the feature's total
+        if (v != 0.f) {
+          s1l[ps] += v;
+          s2l[ps] += v * v;
+        }
+      }
+      __syncthreads();
+    }
+  }
   if (c.standardize) {
     for (int si = t; si < n; si += nthr) {
       atomicAdd(&d.s1[lid_s[si]], s1l[si]);
@@ -982,7 +1019,7 @@ void wide_launch_plan(const WideCfg& c, const WideDev& d, hipStream_t s) {
 void wide_launch_prepare(const WideCfg& c, const WideDev& d, hipStream_t s) {
   const int G = ngroups(c, d);
   wide_assign_kernel<<<grid_for(c.umax, 1024), 256, 0, s>>>(c, d);
-  wide_stats_kernel<<<G, 256, (size_t)d.EB * 12, s>>>(c, d);
+  wide_stats_kernel<<<G, 256, (size_t)d.EB * 16, s>>>(c, d);
   wide_prep_kernel<<<grid_for(d.PLmax, 1024), 256, 0, s>>>(c, d);
 }
 
@@ -1077,7 +1114,7 @@ void wide_prepare_kernels() {
 }
 
 size_t wide_persist_lds(const WideCfg& c, const WideDev& d) {
-  const size_t plan = (size_t)(2 * d.TS + d.EB) * 4, stats = (size_t)d.EB * 12, fb = (size_t)d.EB * c.KP * 4;
+  const size_t plan = (size_t)(2 * d.TS + d.EB) * 4, stats = (size_t)d.EB * 16, fb = (size_t)d.EB * c.KP * 4;
   size_t m = plan > stats ? plan : stats;
   return m > fb ? m : fb;
 }

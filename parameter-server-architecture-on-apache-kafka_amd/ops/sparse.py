@@ -207,6 +207,14 @@ class WideSolveOp:
             return 0, 0
         return self._native.table_ptr, self._native.table_mask
 
+    @property
+    def geometry(self) -> tuple[int, int, int]:
+        """(RB, NQ, KP) the device solve kernels run with: rows per plan group, the
+        non-zeros-per-lane template variant (1, 2, 4 or 8) and the padded class count."""
+        nq = -(-self.NZ // 64)
+        return (int(_native.hip().wide_rows_per_group(self.NZ, self.spec.KP)),
+                next(v for v in (1, 2, 4, 8) if nq <= v), self.spec.KP)
+
     def run(self, ring: SparseRing, B: int, start: int, w_old: torch.Tensor):
         if B <= 0:
             raise ValueError("local solve on an empty buffer")

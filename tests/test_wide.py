@@ -17,8 +17,8 @@ from psx.ops.sparse import (SparseDelta, SparseRing, WideEvalSet, WideSolveOp, n
 from psx.utils.data import load_libsvm, save_libsvm, synth_sparse
 
 
-def _problem(F=3000, rows=400, labels="finefood", seed=0):
-    ds = synth_sparse(rows, num_features=F, labels=labels, nnz_mean=20, max_nnz=48, seed=seed, vocab=4 * F,
+def _problem(F=3000, rows=400, labels="finefood", seed=0, max_nnz=48, nnz_mean=20):
+    ds = synth_sparse(rows, num_features=F, labels=labels, nnz_mean=nnz_mean, max_nnz=max_nnz, seed=seed, vocab=4 * F,
                       class_vocab=200, signal=0.3)
     K = 1 if labels == "binary" else 6
     return ds, WideSpec(F, K)
@@ -275,12 +275,12 @@ def test_gpu_sparse_ring_ingest(cuda):
 
 # ---------------------------------------------------------------------------
 # engines
-def _wide_cfg(N, c, device_iters=6, sigmoid=False):
+def _wide_cfg(N, c, device_iters=6, sigmoid=False, ring_nz=0):
     from psx.runtime.config import PSConfig
 
     return PSConfig(num_workers=N, consistency_model=c, producer_time_per_event=0, stream_mode="per_iter",
                     rows_per_iter=64, epochs=50, max_iters=device_iters, min_buffer_size=64, max_buffer_size=256,
-                    init="random", sigmoid=sigmoid, solver=SolverOptions(zero_const=False))
+                    init="random", sigmoid=sigmoid, solver=SolverOptions(zero_const=False), ring_nz=ring_nz)
 
 
 @pytest.mark.parametrize("c,N", [(0, 1), (0, 2), (-1, 2), (2, 3)])
@@ -361,17 +361,18 @@ def test_ingest_batch_groups_jobs():
     assert len(flushed) == 1 and len(flushed[0]) == 3 and len(b.jobs) == 1
 
 
-def _wide_lanes_run(dev, N, c, iters=8, env=None):
+def _wide_lanes_run(dev, N, c, iters=8, env=None, **rows_kw):
+    # rows_kw (BENCH_ROWS): the ring rows are then 128 wide as well, whatever the longest drawn row is
     import os
 
     from psx.runtime.engine import LocalEngine
 
-    ds, spec = _problem(F=2000, rows=1600)
-    te, _ = _problem(F=2000, rows=300, seed=7)
+    ds, spec = _problem(F=2000, rows=1600, **rows_kw)
+    te, _ = _problem(F=2000, rows=300, seed=7, **rows_kw)
     old = {k: os.environ.get(k) for k in (env or {})}
     os.environ.update(env or {})
     try:
-        eng = LocalEngine(_wide_cfg(N, c, iters), dev, train=ds, test=te)
+        eng = LocalEngine(_wide_cfg(N, c, iters, ring_nz=128 if rows_kw else 0), dev, train=ds, test=te)
         out = eng.run(close_log=False)
     finally:
         for k, v in old.items():
@@ -384,23 +385,28 @@ def _wide_lanes_run(dev, N, c, iters=8, env=None):
     return eng, out, book, te
 
 
+BENCH_ROWS = dict(max_nnz=128, nnz_mean=48)  # bench.py's rows: NZ = 128, two non-zeros per lane
+
+
 @pytest.mark.gpu
-@pytest.mark.parametrize("c,overlay", [(0, "1"), (-1, "1"), (2, "1"), (-1, "0")])
-def test_gpu_wide_lanes_match_cpu_rounds(cuda, c, overlay):
+@pytest.mark.parametrize("c,overlay,N,iters,rows_kw", [(0, "1", 4, 8, {}), (-1, "1", 4, 8, {}), (2, "1", 4, 8, {}),
+                                                      (-1, "0", 4, 8, {}), (-1, "1", 2, 3, BENCH_ROWS)],
+                         ids=["0-1", "-1-1", "2-1", "-1-0", "-1-1-nz128"])
+def test_gpu_wide_lanes_match_cpu_rounds(cuda, c, overlay, N, iters, rows_kw):
     """Several wide workers in ONE solve launch per round (WideLanes, one XCD each):
     every round's solves start from the same server weights and the pushes are applied
     in order, so BSP, SSP and ASP all land on the weights of the CPU engine's BSP rounds
     (whose workers solve with the float64-oracle path, ops/sparse.py _run_cpu).
     overlay "1": the evaluation reads the overlay table and the pushes are applied in
     one launch over it; "0": bitmaps + table probes and one launch per push."""
-    N, iters = 4, 8
     eng, out, book, te = _wide_lanes_run(cuda, N, c, iters, env={"PSX_WIDE_EVAL_OVERLAY": overlay,
-                                                                   "PSX_WIDE_LANES": "1"})
+                                                                   "PSX_WIDE_LANES": "1"}, **rows_kw)
+    assert not rows_kw or eng.workers[0].solver.NZ == 128  # wide_lanes_kernel<KP, 2>
     assert out.get("wide_lanes") == N, out  # the one-launch path ran
     assert out["updates"] == N * iters
     assert len(book.worker) == N * iters and len(book.server) == iters
     assert all(math.isfinite(r[3]) and r[3] > 0 for r in book.worker), "worker rows carry the solve loss"
-    ref, _, _, _ = _wide_lanes_run("cpu", N, 0, iters)
+    ref, _, _, _ = _wide_lanes_run("cpu", N, 0, iters, **rows_kw)
     wc, wg = ref.server.w.cpu(), eng.server.w.cpu()
     assert (wc - wg).abs().max().item() < 5e-3 * wc.abs().max().item()
     # the last server row (the flush pass) evaluates the final global model
@@ -408,15 +414,12 @@ def test_gpu_wide_lanes_match_cpu_rounds(cuda, c, overlay):
     assert abs(book.server[-1][3] - float(conf.trace() / conf.sum())) < 2e-3
 
 
-@pytest.mark.gpu
-def test_gpu_wide_lanes_rows_equal_separate_passes(cuda):
-    """The multi-model evaluation pass: every worker row equals the worker's local model
-    evaluated on its own (the overlay pass of test_gpu_wide_eval_overlay)."""
+def _lanes_rows_equal_separate_passes(cuda, N, **rows_kw):
     from psx.utils.logsink import LogSink
 
-    N = 3
-    eng, out, book, te = _wide_lanes_run(cuda, N, -1, 1, env={"PSX_WIDE_LANES": "1"})
+    eng, out, book, te = _wide_lanes_run(cuda, N, -1, 1, env={"PSX_WIDE_LANES": "1"}, **rows_kw)
     assert out.get("wide_lanes") == N
+    assert not rows_kw or eng.workers[0].solver.NZ == 128  # wide_lanes_kernel<KP, 2>
     # one round from the initial weights: rebuild them and evaluate each local model alone
     w0 = eng.spec.init("random", seed=eng.cfg.seed, device=cuda)
     ev = WideEvalSet(eng.spec, te, cuda)
@@ -428,6 +431,19 @@ def test_gpu_wide_lanes_rows_equal_separate_passes(cuda):
     rows = sorted(book.worker, key=lambda r: r[1])
     for a, b in zip(rows, sorted(alone, key=lambda r: r[1])):
         assert a[1] == b[1] and a[3:6] == b[3:6], (a, b)  # partition, loss, F1, accuracy
+
+
+@pytest.mark.gpu
+def test_gpu_wide_lanes_rows_equal_separate_passes(cuda):
+    """The multi-model evaluation pass: every worker row equals the worker's local model
+    evaluated on its own (the overlay pass of test_gpu_wide_eval_overlay)."""
+    _lanes_rows_equal_separate_passes(cuda, 3)
+
+
+@pytest.mark.gpu
+def test_gpu_wide_lanes_rows_equal_separate_passes_nz128(cuda):
+    """The same at the benchmark's row width (wide_lanes_kernel<8, 2>, NZ = 128)."""
+    _lanes_rows_equal_separate_passes(cuda, 2, **BENCH_ROWS)
 
 
 def test_cli_libsvm_inprocess(tmp_path):
