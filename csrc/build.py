@@ -131,7 +131,7 @@ def build_hip(force=False, jobs=8):
                      glob.glob(os.path.join(CSRC, "comm", "*.h")) + glob.glob(os.path.join(CSRC, "runtime", "*.h")) +
                      [os.path.join(CSRC, "host", "capi.h"), os.path.join(CSRC, "host", "ctrl.h"),
                      os.path.join(CSRC, "host", "sink_record.h"), os.path.join(CSRC, "host", "server_protocol.h"),
-                     os.path.join(CSRC, "host", "lanes_protocol.h")])
+                     os.path.join(CSRC, "host", "lanes_protocol.h"), os.path.join(CSRC, "host", "shard_feed.h")])
     out = os.path.join(PKG, "_psx_hip" + _ext_suffix())
     cflags = [
         "-O3",

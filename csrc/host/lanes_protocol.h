@@ -15,17 +15,16 @@
 // csrc/tests/host_selftest.cc pins the protocol with a scripted plane and clock.
 #pragma once
 #include <algorithm>
-#include <chrono>
 #include <cmath>
 #include <cstdint>
 #include <cstring>
 #include <stdexcept>
 #include <string>
-#include <thread>
 #include <vector>
 
 #include "../kernels/lanes_records.h"
 #include "capi.h"
+#include "shard_feed.h"
 
 namespace psx {
 
@@ -75,10 +74,10 @@ struct LanesHostCfg {
   }
 };
 
-// What the protocol needs of the persistent launch and of the machine.
-class AsyncLanesPlane {
+// What the protocol needs of the persistent launch and of the machine (the clocks and the
+// idle sleep: HostClock).
+class AsyncLanesPlane : public HostClock {
  public:
-  virtual ~AsyncLanesPlane() = default;
   // lane `lane`'s release record number `tag` (its count of records so far)
   virtual void write_release(int lane, const RelRec& q, unsigned tag) = 0;
   // the token ring's slot of ticket n (the token is there once its tag == (unsigned)n)
@@ -92,16 +91,6 @@ class AsyncLanesPlane {
   virtual void begin_pull(int lane) = 0;
   virtual bool pull_done(int lane) = 0;
   virtual void send_delta(int lane) = 0;
-  // wall clock (epoch ms: the producer clock and the deadline), a steady clock, idle sleep
-  virtual double now_ms() {
-    using namespace std::chrono;
-    return (double)duration_cast<microseconds>(system_clock::now().time_since_epoch()).count() / 1000.0;
-  }
-  virtual int64_t mono_ns() {
-    using namespace std::chrono;
-    return duration_cast<nanoseconds>(steady_clock::now().time_since_epoch()).count();
-  }
-  virtual void idle_sleep(int us) { std::this_thread::sleep_for(std::chrono::microseconds(us)); }
 };
 
 class AsyncLanesProtocol {
@@ -125,20 +114,14 @@ class AsyncLanesProtocol {
   };
 
   // Once, before the first run.  cfg stays the caller's (the sink and log_worker change
-  // between runs; lane_leave writes log_worker back); cap: rows of a lane's ring; peer:
-  // releases carry the lane's pull tag; the four vectors are the producer state the
-  // caller shares with its BSP loop.
-  void bind(LanesHostCfg* cfg, int64_t cap, bool peer, AsyncLanesPlane* plane, std::vector<int64_t>* local_total,
-            std::vector<int64_t>* next_local, std::vector<int64_t>* seen_at_solve, std::vector<double>* times) {
+  // between runs; lane_leave writes log_worker back); peer: releases carry the lane's pull
+  // tag; feeds: every lane's producer, the caller's (its BSP loop delivers from them too).
+  void bind(LanesHostCfg* cfg, bool peer, AsyncLanesPlane* plane, std::vector<ShardFeed>* feeds) {
     cfg_ = cfg;
     api_ = reinterpret_cast<const HostApi*>(cfg->api);
-    cap_ = cap;
     peer_ = peer;
     plane_ = plane;
-    local_total_ = local_total;
-    next_local_ = next_local;
-    seen_at_solve_ = seen_at_solve;
-    times_ = times;
+    feeds_ = feeds;
     const int L = cfg->L;
     relc_.assign(L, 0);
     pend_r_.assign(L, LaneRound{});
@@ -416,12 +399,9 @@ class AsyncLanesProtocol {
     __builtin_ia32_pause();
 #endif
   }
-  bool exhausted(int lane) const { return (*next_local_)[lane] >= (*local_total_)[lane] * cfg_->epochs; }
-  bool window_empty(int l) const {
-    int64_t size = 0, start = 0, sn = 0;
-    check(api().window_state(reinterpret_cast<void*>(cfg_->window[l]), &size, &start, &sn), "window state");
-    return size <= 0;
-  }
+  ShardFeed& feed(int lane) const { return (*feeds_)[lane]; }
+  bool exhausted(int lane) const { return feed(lane).exhausted(); }
+  bool window_empty(int l) const { return feed(l).window().size <= 0; }
   bool at_budget(int l) const { return !budget_->empty() && lane_started_[l] >= (*budget_)[l]; }
 
   // the pending new rows of a lane as <= 2 contiguous runs (LaneRound n / n2)
@@ -465,43 +445,17 @@ class AsyncLanesProtocol {
   // Deliver lane `lane`'s due rows into its window (WorkerSamplingProcessor.java:50-113
   // through the host runtime's SlidingWindow) and add them to the lane's pending runs.
   int64_t poll_async(int lane, double now_ms) {
-    if (exhausted(lane)) return 0;
-    const int k = cfg_->k[lane];
-    const int64_t lt = (*local_total_)[lane];
-    int64_t& nl = (*next_local_)[lane];
-    std::vector<double>& times = *times_;
-    const int64_t limit = lt * cfg_->epochs - nl;
-    int64_t n;
-    if (cfg_->per_iter_rows > 0) {
-      n = cfg_->per_iter_rows < limit ? cfg_->per_iter_rows : limit;
-      times.assign((size_t)n, now_ms);
-    } else {
-      const int64_t epoch = nl / lt, cur = nl - epoch * lt;
-      int64_t mx = limit < lt - cur ? limit : lt - cur;
-      if (mx > (int64_t(1) << 22)) mx = int64_t(1) << 22;
-      times.resize(mx > 0 ? (size_t)mx : 1);
-      n = api().due_rows(k, cfg_->N, cfg_->p_ms, cfg_->ds_rows, cur, now_ms, mx, times.data());
-      check(n, "due_rows");
-    }
-    if (n <= 0) return 0;
-    const int64_t first = api().window_insert_many(reinterpret_cast<void*>(cfg_->window[lane]), times.data(), n);
-    check(first, "window insert");
-    const int64_t cap = cap_;
-    const int64_t keep = n < cap ? n : cap, skip = n - keep;
     LaneRound& r = pend_r_[lane];
-    const int64_t tot = (int64_t)r.n + r.n2 + keep;
-    if (tot > cap) drop_front(r, tot - cap, cap);  // rows the ring overwrites before the next solve
-    int64_t slot = (first + skip) % cap, pos = nl + skip, remaining = keep;
-    while (remaining > 0) {  // split at the shard's epoch boundaries
-      const int64_t cur = pos % lt;
-      const int64_t run = remaining < lt - cur ? remaining : lt - cur;
-      append_run(r, k + cur * (int64_t)cfg_->N, cfg_->N, slot, run, cap);
-      slot = (slot + run) % cap;
-      pos += run;
-      remaining -= run;
-    }
-    nl += n;
-    return n;
+    const int64_t cap = feed(lane).cap();
+    return feed(lane).deliver(
+        now_ms,
+        [&](int64_t keep) {  // rows the ring overwrites before the next solve
+          const int64_t tot = (int64_t)r.n + r.n2 + keep;
+          if (tot > cap) drop_front(r, tot - cap, cap);
+        },
+        [&](int64_t src_first, int64_t step, int64_t run, int64_t slot) {
+          append_run(r, src_first, step, slot, run, cap);
+        });
   }
 
   // Start lane `lane` at clock vc if the cadence lets it go: its release record (window,
@@ -509,24 +463,23 @@ class AsyncLanesProtocol {
   // after the latest applied update; remote: the lane's receive slot.
   bool try_release(int lane, int64_t vc, double now_ms, int64_t snap = -1) {
     poll_async(lane, now_ms);
-    int64_t size = 0, start = 0, sn = 0;
-    check(api().window_state(reinterpret_cast<void*>(cfg_->window[lane]), &size, &start, &sn), "window state");
-    const int64_t need = cfg_->new_tuples_needed(size, vc);  // (vc: the worker's completed pushes)
-    if (!(size > 0 && (need <= 0 || sn - (*seen_at_solve_)[lane] >= need || exhausted(lane)))) return false;
-    (*seen_at_solve_)[lane] = sn;
+    const ShardFeed::Window v = feed(lane).window();
+    // (vc: the worker's completed pushes)
+    if (!feed(lane).solve_due(v, cfg_->new_tuples_needed(v.size, vc))) return false;
+    feed(lane).mark_solved(v.seen);
     RelRec q;
     std::memset(&q, 0, sizeof(q));
     q.vc = vc;
     q.snap = snap >= 0 ? (long long)snap : (long long)aticket_;
     q.r = pend_r_[lane];
-    q.r.B = (int)size;
-    q.r.start = (int)start;
+    q.r.B = (int)v.size;
+    q.r.start = (int)v.start;
     if (q.r.n == 0) q.r.step = cfg_->N;
     pend_r_[lane] = LaneRound{};
     RunRec& rr = runrec_[lane];
     rr = RunRec{};
     rr.vc = vc;
-    rr.nseen = sn;
+    rr.nseen = v.seen;
     rr.snap = q.snap;
     rr.r = q.r;
     if (cfg_->sink) {
@@ -629,10 +582,8 @@ class AsyncLanesProtocol {
   LanesHostCfg* cfg_ = nullptr;
   const HostApi* api_ = nullptr;
   AsyncLanesPlane* plane_ = nullptr;
-  int64_t cap_ = 0;
   bool peer_ = false;
-  std::vector<int64_t>*local_total_ = nullptr, *next_local_ = nullptr, *seen_at_solve_ = nullptr;
-  std::vector<double>* times_ = nullptr;
+  std::vector<ShardFeed>* feeds_ = nullptr;
   uint64_t aticket_ = 0;                // last ticket applied
   std::vector<uint64_t> relc_;          // release records written per lane
   std::vector<LaneRound> pend_r_;       // new stream rows not yet in the lane's ring

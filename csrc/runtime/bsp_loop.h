@@ -29,13 +29,15 @@
 #include <hip/hip_runtime.h>
 
 #include <cstdint>
-#include <vector>
 
 #include "../comm/rccl_comm.h"
 #include "../host/capi.h"
+#include "../host/shard_feed.h"
 #include "../solver/solver.h"
 
 namespace psx {
+
+constexpr double kBspRowWaitS = 600.0;  // how long a round waits for the worker's first rows
 
 struct BspLoopCfg {
   // producer (worker k of N reads dataset rows k, k + N, ...; `epochs` passes)
@@ -94,9 +96,9 @@ class BspLoop {
   int64_t run(int64_t rounds, int64_t r0, hipStream_t stream);
   // Evaluate the deferred rows of the last round (standalone launch).
   void flush(hipStream_t stream);
-  int64_t next_local() const { return next_local_; }
-  void set_next_local(int64_t v) { next_local_ = v; }
-  bool exhausted() const { return next_local_ >= local_total_ * cfg_.epochs; }
+  int64_t next_local() const { return feed_.next_local(); }
+  void set_next_local(int64_t v) { feed_.set_next_local(v); }
+  bool exhausted() const { return feed_.exhausted(); }
   int64_t updates() const { return updates_; }
   double host_us_per_round() const { return rounds_run_ ? host_ns_ / 1000.0 / (double)rounds_run_ : 0.0; }
 
@@ -109,8 +111,8 @@ class BspLoop {
   RcclComm* comm_;
   BspLoopCfg cfg_;
   const HostApi* api_;
-  int64_t local_total_ = 0, next_local_ = 0;
-  std::vector<double> times_;
+  ShardFeed feed_;  // the producer: what is due, where it lands (csrc/host/shard_feed.h)
+  HostClock clock_;
   BspRow pend_w_, pend_s_;
   int64_t updates_ = 0, rounds_run_ = 0;
   double host_ns_ = 0.0;

@@ -1,25 +1,12 @@
 // Native BSP round loop (see bsp_loop.h).
 #include "bsp_loop.h"
 
-#include <chrono>
 #include <stdexcept>
 #include <string>
-#include <thread>
 
 #include "../kernels/lr_kernels.h"
 
 namespace psx {
-
-namespace {
-double epoch_ms() {
-  using namespace std::chrono;
-  return (double)duration_cast<microseconds>(system_clock::now().time_since_epoch()).count() / 1000.0;
-}
-int64_t steady_ns() {
-  using namespace std::chrono;
-  return duration_cast<nanoseconds>(steady_clock::now().time_since_epoch()).count();
-}
-}  // namespace
 
 BspLoop::BspLoop(LocalSolver* solver, RcclComm* comm, const BspLoopCfg& cfg)
     : solver_(solver), comm_(comm), cfg_(cfg), api_(reinterpret_cast<const HostApi*>(cfg.api)) {
@@ -40,8 +27,9 @@ BspLoop::BspLoop(LocalSolver* solver, RcclComm* comm, const BspLoopCfg& cfg)
     throw std::invalid_argument("BspLoop: bad evaluation set / worker fragments");
   if (solver_->rows_mode() || !solver_->eager())
     throw std::invalid_argument("BspLoop: needs the eager small-window solver");
-  local_total_ = cfg_.ds_rows > cfg_.k ? (cfg_.ds_rows - cfg_.k + cfg_.N - 1) / cfg_.N : 0;
-  if (local_total_ == 0) throw std::invalid_argument("BspLoop: worker has no rows");
+  feed_ = ShardFeed({cfg_.k, cfg_.N, cfg_.ds_rows, cfg_.epochs, cfg_.per_iter_rows, cfg_.p_ms, cfg_.window, cfg_.cap,
+                     api_, "BspLoop: "});
+  if (feed_.local_total() == 0) throw std::invalid_argument("BspLoop: worker has no rows");
 }
 
 void BspLoop::check(int64_t rc, const char* what) const {
@@ -58,71 +46,35 @@ void BspLoop::acquire(uint64_t* seq, uintptr_t* addr, int* slot) {
 // ring by a ring-ingest launch; the last run is handed to the solve's first
 // kernel (*fused) when it fits.  Returns the number of rows delivered.
 int64_t BspLoop::poll(double now_ms, RingIngest* fused, hipStream_t stream) {
-  if (exhausted()) return 0;
-  const int64_t limit = local_total_ * cfg_.epochs - next_local_;
-  int64_t n;
-  if (cfg_.per_iter_rows > 0) {
-    n = cfg_.per_iter_rows < limit ? cfg_.per_iter_rows : limit;
-    times_.assign((size_t)n, now_ms);
-  } else {
-    const int64_t epoch = next_local_ / local_total_;
-    const int64_t cur = next_local_ - epoch * local_total_;
-    int64_t mx = limit < local_total_ - cur ? limit : local_total_ - cur;
-    if (mx > (int64_t(1) << 22)) mx = int64_t(1) << 22;
-    times_.resize(mx > 0 ? (size_t)mx : 1);
-    n = api().due_rows(cfg_.k, cfg_.N, cfg_.p_ms, cfg_.ds_rows, cur, now_ms, mx, times_.data());
-    check(n, "due_rows");
-  }
-  if (n <= 0) return 0;
-  const int64_t first = api().window_insert_many(reinterpret_cast<void*>(cfg_.window), times_.data(), n);
-  check(first, "window insert");
-  const int64_t cap = cfg_.cap;
-  const int64_t keep = n < cap ? n : cap;  // only the last cap rows can survive in the window
-  const int64_t skip = n - keep;
-  int64_t slot = (first + skip) % cap, pos = next_local_ + skip, remaining = keep;
-  while (remaining > 0) {  // split at the shard's epoch boundaries
-    const int64_t cur = pos % local_total_;
-    const int64_t run = remaining < local_total_ - cur ? remaining : local_total_ - cur;
-    const int64_t src_first = cfg_.k + cur * cfg_.N;
-    if (run == remaining && run <= kMaxFusedIngest) {
-      *fused = RingIngest{cfg_.dsX, cfg_.dsy, (long long)src_first, (long long)cfg_.N, (int)run, (int)slot};
-    } else {
-      launch_ring_ingest(cfg_.dsX, cfg_.dsy, src_first, cfg_.N, run, cfg_.X, cfg_.XT, cfg_.y, slot, cap, cfg_.Fp,
-                         stream);
-    }
-    slot = (slot + run) % cap;
-    pos += run;
-    remaining -= run;
-  }
-  next_local_ += n;
-  return n;
+  int64_t left = 0;
+  return feed_.deliver(
+      now_ms, [&](int64_t keep) { left = keep; },
+      [&](int64_t src_first, int64_t step, int64_t run, int64_t slot) {
+        left -= run;
+        if (left == 0 && run <= kMaxFusedIngest)
+          *fused = RingIngest{cfg_.dsX, cfg_.dsy, (long long)src_first, (long long)step, (int)run, (int)slot};
+        else
+          launch_ring_ingest(cfg_.dsX, cfg_.dsy, src_first, step, run, cfg_.X, cfg_.XT, cfg_.y, slot, cfg_.cap,
+                             cfg_.Fp, stream);
+      });
 }
 
 int64_t BspLoop::run(int64_t rounds, int64_t r0, hipStream_t stream) {
-  const int64_t t_begin = steady_ns();
+  const int64_t t_begin = clock_.mono_ns();
   const int64_t KF = (int64_t)cfg_.K * cfg_.Fp;
   const int64_t P = KF + cfg_.K;
-  void* win = reinterpret_cast<void*>(cfg_.window);
+  const RoundGate gate{&clock_, cfg_.t0_ms, kBspRowWaitS, "BspLoop: no rows for 600 s"};
   void* sink = reinterpret_cast<void*>(cfg_.sink);
   int64_t done = 0;
   for (; done < rounds; ++done) {
     const int64_t r = r0 + done;
-    const double now = epoch_ms();
-    RingIngest ing{};
-    poll(now - cfg_.t0_ms, &ing, stream);
-    int64_t size = 0, start = 0, seen = 0;
-    check(api().window_state(win, &size, &start, &seen), "window state");
     // no rows yet: wait for the producer as the Python loop does (a poll that
     // delivers anything makes the window non-empty, so no staged run is lost);
     // an exhausted stream with an empty window ends the run
-    const double wait0 = epoch_ms();
-    while (size <= 0 && !exhausted()) {
-      if (epoch_ms() - wait0 > 600e3) throw std::runtime_error("BspLoop: no rows for 600 s");
-      std::this_thread::sleep_for(std::chrono::microseconds(500));
-      poll(epoch_ms() - cfg_.t0_ms, &ing, stream);
-      check(api().window_state(win, &size, &start, &seen), "window state");
-    }
-    if (size <= 0) break;
+    RingIngest ing{};
+    ShardFeed::Window v;
+    if (!gate.wait(&feed_, 1, &v, [&](double now) { poll(now, &ing, stream); })) break;
+    const int64_t size = v.size, start = v.start, seen = v.seen;
     // ---- the previous round's rows ride in this solve ----
     EvalRide ride{};
     bool riding = false;
@@ -199,7 +151,7 @@ int64_t BspLoop::run(int64_t rounds, int64_t r0, hipStream_t stream) {
   }
   rounds_run_ += done;
   updates_ += done;
-  host_ns_ += (double)(steady_ns() - t_begin);
+  host_ns_ += (double)(clock_.mono_ns() - t_begin);
   return done;
 }
 

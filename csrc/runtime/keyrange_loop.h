@@ -40,6 +40,7 @@
 
 #include "../comm/rccl_comm.h"
 #include "../host/capi.h"
+#include "../host/shard_feed.h"
 #include "../kernels/wide_kernels.h"
 #include "../solver/wide_solver.h"
 
@@ -118,9 +119,9 @@ class KeyRangeLoop {
   int64_t last_round_bytes() const { return last_round_bytes_; }
   // distinct features of the last window (after a synchronisation at world 1)
   int64_t last_u() const;
-  int64_t next_local() const { return next_local_; }
-  void set_next_local(int64_t v) { next_local_ = v; }
-  bool exhausted() const { return next_local_ >= local_total_ * cfg_.epochs; }
+  int64_t next_local() const { return feed_.next_local(); }
+  void set_next_local(int64_t v) { feed_.set_next_local(v); }
+  bool exhausted() const { return feed_.exhausted(); }
   double host_us_per_round() const { return rounds_run_ ? host_ns_ / 1000.0 / (double)rounds_run_ : 0.0; }
   int64_t rounds_run() const { return rounds_run_; }
   size_t device_bytes() const { return ws_bytes_ + solver_->workspace_bytes(); }
@@ -153,8 +154,8 @@ class KeyRangeLoop {
   unsigned* ticket_ = nullptr;
   unsigned* cnt_dev_ = nullptr;  // [2W]: recv counts
   unsigned* cnt_host_ = nullptr; // pinned [2W]: send counts, recv counts
-  int64_t local_total_ = 0, next_local_ = 0;
-  std::vector<double> times_;
+  ShardFeed feed_;  // the producer: what is due, where it lands (csrc/host/shard_feed.h)
+  HostClock clock_;
   bool margins_ready_ = false;
   int64_t model_bytes_ = 0, eval_bytes_ = 0, last_round_bytes_ = 0;
   int64_t rounds_run_ = 0;

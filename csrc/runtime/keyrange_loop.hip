@@ -1,12 +1,10 @@
 // Native key-range sharded BSP loop (see keyrange_loop.h).
 #include "keyrange_loop.h"
 
-#include <chrono>
 #include <cstdlib>
 #include <cstring>
 #include <stdexcept>
 #include <string>
-#include <thread>
 
 #include "../kernels/common.h"
 #include "../kernels/keyrange_kernels.h"
@@ -15,14 +13,6 @@
 namespace psx {
 
 namespace {
-double epoch_ms() {
-  using namespace std::chrono;
-  return (double)duration_cast<microseconds>(system_clock::now().time_since_epoch()).count() / 1000.0;
-}
-int64_t steady_ns() {
-  using namespace std::chrono;
-  return duration_cast<nanoseconds>(steady_clock::now().time_since_epoch()).count();
-}
 size_t align_up(size_t v, size_t a) { return (v + a - 1) / a * a; }
 }  // namespace
 
@@ -49,8 +39,9 @@ KeyRangeLoop::KeyRangeLoop(const KeyRangeLoopCfg& cfg, RcclComm* comm)
   if (evaluates && (!cfg_.t_indptr || !cfg_.t_idx || !cfg_.t_val || !cfg_.t_y || cfg_.T <= 0 || !cfg_.s_indptr ||
                     !cfg_.s_idx || !cfg_.s_val))
     throw std::invalid_argument("KeyRangeLoop: no test set");
-  local_total_ = cfg_.ds_rows > cfg_.k ? (cfg_.ds_rows - cfg_.k + cfg_.N - 1) / cfg_.N : 0;
-  if (local_total_ == 0) throw std::invalid_argument("KeyRangeLoop: the worker has no rows");
+  feed_ = ShardFeed({cfg_.k, cfg_.N, cfg_.ds_rows, cfg_.epochs, cfg_.per_iter_rows, cfg_.p_ms, cfg_.window, c.cap, api_,
+                     "KeyRangeLoop: "});
+  if (feed_.local_total() == 0) throw std::invalid_argument("KeyRangeLoop: the worker has no rows");
   c.pulled = W_ > 1 ? 1 : 0;  // world 1: the solve reads the (whole) shard in place
   c.own_W = W_;
   c.own_S = S_;
@@ -132,39 +123,11 @@ int64_t KeyRangeLoop::last_u() const { return (int64_t)solver_->ucount_host(); }
 // 50-113 through the host runtime's SlidingWindow; the rows are gathered from
 // the resident CSR dataset, split at the shard's epoch boundaries).
 int64_t KeyRangeLoop::poll(double now_ms, hipStream_t stream) {
-  if (exhausted()) return 0;
-  const int64_t lt = local_total_;
-  const int64_t limit = lt * cfg_.epochs - next_local_;
-  int64_t n;
-  if (cfg_.per_iter_rows > 0) {
-    n = cfg_.per_iter_rows < limit ? cfg_.per_iter_rows : limit;
-    times_.assign((size_t)n, now_ms);
-  } else {
-    const int64_t epoch = next_local_ / lt, cur = next_local_ - epoch * lt;
-    int64_t mx = limit < lt - cur ? limit : lt - cur;
-    if (mx > (int64_t(1) << 22)) mx = int64_t(1) << 22;
-    times_.resize(mx > 0 ? (size_t)mx : 1);
-    n = api().due_rows(cfg_.k, cfg_.N, cfg_.p_ms, cfg_.ds_rows, cur, now_ms, mx, times_.data());
-    check(n, "due_rows");
-  }
-  if (n <= 0) return 0;
-  const int64_t first = api().window_insert_many(reinterpret_cast<void*>(cfg_.window), times_.data(), n);
-  check(first, "window insert");
-  const int64_t cap = cfg_.wcfg.cap;
-  const int64_t keep = n < cap ? n : cap, skip = n - keep;
-  int64_t slot = (first + skip) % cap, pos = next_local_ + skip, remaining = keep;
-  while (remaining > 0) {
-    const int64_t cur = pos % lt;
-    const int64_t run = remaining < lt - cur ? remaining : lt - cur;
-    launch_sparse_ring_ingest(cfg_.indptr, cfg_.idx, cfg_.val, cfg_.y, cfg_.k + cur * (int64_t)cfg_.N, cfg_.N, run,
-                              cfg_.ridx, cfg_.rval, cfg_.rnnz, cfg_.ry, slot, (int)cap, cfg_.wcfg.NZ, cfg_.trunc,
-                              stream);
-    slot = (slot + run) % cap;
-    pos += run;
-    remaining -= run;
-  }
-  hip_check(hipGetLastError(), "sparse ring ingest");
-  next_local_ += n;
+  const int64_t n = feed_.deliver(now_ms, [&](int64_t src_first, int64_t step, int64_t run, int64_t slot) {
+    launch_sparse_ring_ingest(cfg_.indptr, cfg_.idx, cfg_.val, cfg_.y, src_first, step, run, cfg_.ridx, cfg_.rval,
+                              cfg_.rnnz, cfg_.ry, slot, cfg_.wcfg.cap, cfg_.wcfg.NZ, cfg_.trunc, stream);
+  });
+  if (n > 0) hip_check(hipGetLastError(), "sparse ring ingest");
   return n;
 }
 
@@ -203,7 +166,8 @@ void KeyRangeLoop::exchange(const void* send, const int64_t* soff, const int64_t
 }
 
 int64_t KeyRangeLoop::run(int64_t rounds, int64_t r0, hipStream_t stream, double max_wait_s) {
-  const int64_t t_begin = steady_ns();
+  const int64_t t_begin = clock_.mono_ns();
+  const RoundGate gate{&clock_, cfg_.t0_ms, max_wait_s, "KeyRangeLoop: no rows"};
   const WideCfg& c = cfg_.wcfg;
   const bool evaluates = cfg_.sink && (cfg_.log_server || cfg_.log_workers);
   void* sink = reinterpret_cast<void*>(cfg_.sink);
@@ -218,20 +182,9 @@ int64_t KeyRangeLoop::run(int64_t rounds, int64_t r0, hipStream_t stream, double
     const int par = (int)(r & 1);
     last_round_bytes_ = 0;
     // ---- deliveries, then the window (BSP: every worker has rows) ----
-    int64_t size = 0, start = 0, seen = 0;
-    const double wait0 = epoch_ms();
-    for (;;) {
-      poll(epoch_ms() - cfg_.t0_ms, stream);
-      check(api().window_state(reinterpret_cast<void*>(cfg_.window), &size, &start, &seen), "window state");
-      if (size > 0) break;
-      if (exhausted()) {
-        rounds_run_ += done;
-        host_ns_ += (double)(steady_ns() - t_begin);
-        return done;
-      }
-      if (epoch_ms() - wait0 > max_wait_s * 1000.0) throw std::runtime_error("KeyRangeLoop: no rows");
-      std::this_thread::sleep_for(std::chrono::microseconds(500));
-    }
+    ShardFeed::Window v;
+    if (!gate.wait(&feed_, 1, &v, [&](double now) { poll(now, stream); })) break;
+    const int64_t size = v.size, start = v.start, seen = v.seen;
     const int32_t* ids = cfg_.uniq;
     if (W_ > 1) {
       // ---- plan: the window's features, grouped by owner ----
@@ -325,7 +278,7 @@ int64_t KeyRangeLoop::run(int64_t rounds, int64_t r0, hipStream_t stream, double
     if (cfg_.tracker && rank_ == 0) check(api().tracker_bsp_round(reinterpret_cast<void*>(cfg_.tracker), r), "tracker");
   }
   rounds_run_ += done;
-  host_ns_ += (double)(steady_ns() - t_begin);
+  host_ns_ += (double)(clock_.mono_ns() - t_begin);
   return done;
 }
 

@@ -193,16 +193,16 @@ class LanesLoop : private AsyncLanesPlane {
   // --idle_wait; default 600 s).  A short --worker_timeout then only bounds busy workers.
   void set_idle_wait(double s) { proto_.set_idle_wait(s); }
   void set_lr(float lr) { cfg_.lr = lr; }
-  int64_t next_local(int lane) const { return next_local_.at(lane); }
-  void set_next_local(int lane, int64_t v) { next_local_.at(lane) = v; }
+  int64_t next_local(int lane) const { return feeds_.at(lane).next_local(); }
+  void set_next_local(int lane, int64_t v) { feeds_.at(lane).set_next_local(v); }
   // tuples seen by lane `lane` when its last solve started (the cadence's origin)
-  int64_t seen_at_solve(int lane) const { return seen_at_solve_.at(lane); }
-  void set_seen_at_solve(int lane, int64_t v) { seen_at_solve_.at(lane) = v; }
+  int64_t seen_at_solve(int lane) const { return feeds_.at(lane).seen_at_solve(); }
+  void set_seen_at_solve(int lane, int64_t v) { feeds_.at(lane).set_seen_at_solve(v); }
   // new tuples lane windows of `size` rows wait for (0: no cadence)
   int64_t new_tuples_needed(int64_t size, int64_t updates = -1) const {  // updates < 0: no ramp
     return cfg_.new_tuples_needed(size, updates);
   }
-  bool exhausted(int lane) const { return next_local_[lane] >= local_total_[lane] * cfg_.epochs; }
+  bool exhausted(int lane) const { return feeds_[lane].exhausted(); }
   bool all_exhausted() const;
   int hand_off_scope() const { return S_; }  // 2: one-XCD hand-offs, 1: sc1 (placement check failed)
   // true: a round's rows are evaluated by a launch of their own on a side stream
@@ -294,8 +294,8 @@ class LanesLoop : private AsyncLanesPlane {
   const HostApi* api_;
   int S_ = 2;
   int P_ = 0;
-  std::vector<int64_t> local_total_, next_local_, seen_at_solve_;
-  std::vector<double> times_;
+  std::vector<ShardFeed> feeds_;          // every lane's producer (csrc/host/shard_feed.h), shared with proto_
+  std::vector<ShardFeed::Window> view_;   // the windows the current round solves
   void* ws_ = nullptr;  // device workspace of every lane + shared buffers
   LaneDev* lanes_dev_ = nullptr;
   std::vector<LaneDev> lanes_;

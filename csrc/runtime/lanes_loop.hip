@@ -21,10 +21,6 @@
 namespace psx {
 
 namespace {
-double epoch_ms() {
-  using namespace std::chrono;
-  return (double)duration_cast<microseconds>(system_clock::now().time_since_epoch()).count() / 1000.0;
-}
 int64_t steady_ns() {
   using namespace std::chrono;
   return duration_cast<nanoseconds>(steady_clock::now().time_since_epoch()).count();
@@ -86,11 +82,10 @@ LanesLoop::LanesLoop(const LanesLoopCfg& cfg, Comm* comm)
     const int k = cfg_.k[l];
     if (k < 0 || k >= cfg_.N || !cfg_.X[l] || !cfg_.y[l] || !cfg_.window[l])
       throw std::invalid_argument("LanesLoop: bad lane " + std::to_string(l));
-    const int64_t tot = cfg_.ds_rows > k ? (cfg_.ds_rows - k + cfg_.N - 1) / cfg_.N : 0;
-    if (tot == 0) throw std::invalid_argument("LanesLoop: worker " + std::to_string(k) + " has no rows");
-    local_total_.push_back(tot);
-    next_local_.push_back(0);
-    seen_at_solve_.push_back(0);
+    feeds_.emplace_back(ShardFeed::Cfg{k, cfg_.N, cfg_.ds_rows, cfg_.epochs, cfg_.per_iter_rows, cfg_.p_ms,
+                                       cfg_.window[l], s.cap, api_, "LanesLoop: "});
+    if (feeds_[l].local_total() == 0)
+      throw std::invalid_argument("LanesLoop: worker " + std::to_string(k) + " has no rows");
   }
   prepare_kernels();
   // the lanes claim their XCD at run time (LanesArgs::claim), so placement needs no
@@ -361,60 +356,32 @@ bool LanesLoop::all_exhausted() const {
 // contiguous run go to the round kernel (r->n, dst, first, step), earlier runs
 // (a delivery that wraps the shard's epoch) to a ring-ingest launch.
 int64_t LanesLoop::poll(int lane, double now_ms, LaneRound* r, hipStream_t stream) {
-  if (exhausted(lane)) return 0;
-  const int k = cfg_.k[lane];
-  const int64_t lt = local_total_[lane];
-  int64_t& nl = next_local_[lane];
-  const int64_t limit = lt * cfg_.epochs - nl;
-  int64_t n;
-  if (cfg_.per_iter_rows > 0) {
-    n = cfg_.per_iter_rows < limit ? cfg_.per_iter_rows : limit;
-    times_.assign((size_t)n, now_ms);
-  } else {
-    const int64_t epoch = nl / lt, cur = nl - epoch * lt;
-    int64_t mx = limit < lt - cur ? limit : lt - cur;
-    if (mx > (int64_t(1) << 22)) mx = int64_t(1) << 22;
-    times_.resize(mx > 0 ? (size_t)mx : 1);
-    n = api().due_rows(k, cfg_.N, cfg_.p_ms, cfg_.ds_rows, cur, now_ms, mx, times_.data());
-    check(n, "due_rows");
-  }
-  if (n <= 0) return 0;
-  const int64_t first = api().window_insert_many(reinterpret_cast<void*>(cfg_.window[lane]), times_.data(), n);
-  check(first, "window insert");
   const int64_t cap = cfg_.scfg.cap;
-  // rows already pending for the kernel from an earlier delivery of this round: into
-  // the ring now (the kernel carries at most the last two contiguous runs)
-  flush_ingest(lane, r, stream);
-  const int64_t keep = n < cap ? n : cap, skip = n - keep;
-  int64_t slot = (first + skip) % cap, pos = nl + skip, remaining = keep;
-  while (remaining > 0) {  // split at the shard's epoch boundaries
-    const int64_t cur = pos % lt;
-    const int64_t run = remaining < lt - cur ? remaining : lt - cur;
-    const int64_t src_first = k + cur * (int64_t)cfg_.N;
-    if (r->n2 > 0) {  // a third run: the oldest goes to a launch of its own
-      ovl_wait_last(stream);
-      launch_ring_ingest(cfg_.dsX, cfg_.dsy, r->first, r->step, r->n, reinterpret_cast<uint16_t*>(cfg_.X[lane]),
-                         nullptr, reinterpret_cast<int32_t*>(cfg_.y[lane]), r->dst, cap, cfg_.scfg.Fp, stream);
-      r->dst = (int)((r->dst + r->n) % cap);
-      r->first = r->first2;
-      r->n = r->n2;
-      r->n2 = 0;
-    }
-    if (r->n == 0) {
-      r->first = src_first;
-      r->step = cfg_.N;
-      r->n = (int)run;
-      r->dst = (int)slot;
-    } else {
-      r->first2 = src_first;
-      r->n2 = (int)run;
-    }
-    slot = (slot + run) % cap;
-    pos += run;
-    remaining -= run;
-  }
-  nl += n;
-  return n;
+  return feeds_[lane].deliver(
+      now_ms,
+      // rows already pending for the kernel from an earlier delivery of this round: into
+      // the ring now (the kernel carries at most the last two contiguous runs)
+      [&](int64_t) { flush_ingest(lane, r, stream); },
+      [&](int64_t src_first, int64_t step, int64_t run, int64_t slot) {
+        if (r->n2 > 0) {  // a third run: the oldest goes to a launch of its own
+          ovl_wait_last(stream);
+          launch_ring_ingest(cfg_.dsX, cfg_.dsy, r->first, r->step, r->n, reinterpret_cast<uint16_t*>(cfg_.X[lane]),
+                             nullptr, reinterpret_cast<int32_t*>(cfg_.y[lane]), r->dst, cap, cfg_.scfg.Fp, stream);
+          r->dst = (int)((r->dst + r->n) % cap);
+          r->first = r->first2;
+          r->n = r->n2;
+          r->n2 = 0;
+        }
+        if (r->n == 0) {
+          r->first = src_first;
+          r->step = step;
+          r->n = (int)run;
+          r->dst = (int)slot;
+        } else {
+          r->first2 = src_first;
+          r->n2 = (int)run;
+        }
+      });
 }
 
 void LanesLoop::ovl_wait_last(hipStream_t stream) {
@@ -611,6 +578,8 @@ void LanesLoop::check_errors(int64_t round) {
 int64_t LanesLoop::run(int64_t rounds, int64_t r0, hipStream_t stream, double max_wait_s, double deadline_ms) {
   const int64_t t_begin = steady_ns();
   const int L = cfg_.L;
+  const RoundGate gate{this, cfg_.t0_ms, max_wait_s, "LanesLoop: no rows for a worker", deadline_ms};
+  view_.resize(L);
   const int KF = cfg_.scfg.K * cfg_.scfg.Fp;
   std::vector<int> slots, kinds;
   std::vector<uint64_t> seqs;
@@ -665,40 +634,26 @@ int64_t LanesLoop::run(int64_t rounds, int64_t r0, hipStream_t stream, double ma
     // ---- deliveries, then every lane's window (BSP: wait until all have rows, and
     // with a cadence until all saw enough new tuples, WorkerTrainingProcessor.java:63-98
     // runs on every new tuple; psx/runtime/roles.py:WorkerRole.ready) ----
-    std::vector<int64_t> seen(L, 0);
-    const double wait0 = epoch_ms();
-    for (;;) {
-      const double now = epoch_ms() - cfg_.t0_ms;
-      for (int l = 0; l < L; ++l) poll(l, now, &a.r[l], rs);
-      bool ready = true, rows = true;
-      for (int l = 0; l < L; ++l) {
-        int64_t size = 0, start = 0, sn = 0;
-        check(api().window_state(reinterpret_cast<void*>(cfg_.window[l]), &size, &start, &sn), "window state");
-        a.r[l].B = (int)size;
-        a.r[l].start = (int)start;
-        seen[l] = sn;
-        rows &= size > 0;
-        const int64_t need = new_tuples_needed(size, r);  // (BSP: every lane solved r times)
-        ready &= size > 0 && (need <= 0 || sn - seen_at_solve_[l] >= need || exhausted(l));
-      }
-      if (ready) break;
-      bool end = false;
-      for (int l = 0; l < L; ++l)  // a lane with an empty window and nothing left to come: the run ends
-        end |= a.r[l].B <= 0 && exhausted(l);
-      if (deadline_ms > 0.0 && epoch_ms() >= deadline_ms) end = true;
-      if (end) {
-        for (int l = 0; l < L; ++l)  // rows delivered meanwhile: into the ring now
-          if (a.r[l].n > 0 || a.r[l].n2 > 0) flush_ingest(l, &a.r[l], rs);
-        ovl_join();
-        rounds_run_ += done;
-        host_ns_ += (double)(steady_ns() - t_begin);
-        return done;
-      }
-      if (!rows && epoch_ms() - wait0 > max_wait_s * 1000.0) throw std::runtime_error("LanesLoop: no rows for a worker");
-      std::this_thread::sleep_for(std::chrono::microseconds(500));
+    const bool go = gate.wait(
+        feeds_.data(), L, view_.data(),
+        [&](double now) {
+          for (int l = 0; l < L; ++l) poll(l, now, &a.r[l], rs);
+        },
+        [&](int64_t size) { return new_tuples_needed(size, r); });  // (BSP: every lane solved r times)
+    if (!go) {
+      for (int l = 0; l < L; ++l)  // rows delivered meanwhile: into the ring now
+        if (a.r[l].n > 0 || a.r[l].n2 > 0) flush_ingest(l, &a.r[l], rs);
+      ovl_join();
+      rounds_run_ += done;
+      host_ns_ += (double)(steady_ns() - t_begin);
+      return done;
     }
+    std::vector<int64_t> seen(L, 0);
     for (int l = 0; l < L; ++l) {
-      seen_at_solve_[l] = seen[l];
+      a.r[l].B = (int)view_[l].size;
+      a.r[l].start = (int)view_[l].start;
+      seen[l] = view_[l].seen;
+      feeds_[l].mark_solved(seen[l]);
       a.r[l].delay_us = l < (int)cfg_.delay_us.size() ? cfg_.delay_us[l] : 0;
     }
     phase(0);
@@ -987,7 +942,7 @@ void LanesLoop::ensure_async() {
   const int L = cfg_.L, FP = s.Fp, NS = FP / 32;
   if (L < 1) throw std::invalid_argument("LanesLoop::run_async: no lanes");
   for (int l = 0; l < L; ++l)
-    if (local_total_[l] < s.cap)  // pending rows of one release span at most one epoch wrap
+    if (feeds_[l].local_total() < s.cap)  // pending rows of one release span at most one epoch wrap
       throw std::invalid_argument("LanesLoop::run_async: a worker's shard is smaller than its ring");
   size_t off = 0;
   auto take = [&](size_t bytes) {
@@ -1091,7 +1046,7 @@ void LanesLoop::ensure_async() {
   a.Tv = cfg_.Tv;
   a.tnz = (cfg_.Ti && cfg_.Tv && cfg_.tnz > 0 && cfg_.tnz % 8 == 0) ? cfg_.tnz : 0;
   a.claim = claim_;
-  proto_.bind(&cfg_, s.cap, peer_rx_ != nullptr, this, &local_total_, &next_local_, &seen_at_solve_, &times_);
+  proto_.bind(&cfg_, peer_rx_ != nullptr, this, &feeds_);
 }
 
 void LanesLoop::write_release(int lane, const RelRec& q, unsigned tag) {
@@ -1189,8 +1144,8 @@ std::string LanesLoop::progress_report() {
   if (hipStreamCreateWithFlags(&s, hipStreamNonBlocking) == hipSuccess &&
       hipMemcpyAsync(h, claim_ + 32 * ((launches_ - 1) & 1), 32 * sizeof(unsigned), hipMemcpyDeviceToHost, s) ==
           hipSuccess) {
-    const double t0 = epoch_ms();
-    while (hipStreamQuery(s) == hipErrorNotReady && epoch_ms() - t0 < 2000.0)
+    const double t0 = now_ms();
+    while (hipStreamQuery(s) == hipErrorNotReady && now_ms() - t0 < 2000.0)
       std::this_thread::sleep_for(std::chrono::microseconds(100));
     if (hipStreamQuery(s) == hipSuccess) {
       m += "; lane slots claimed per XCD:";
@@ -1224,12 +1179,12 @@ void LanesLoop::stop_all(hipStream_t stream) {
   proto_.stop_lanes();
   // the launch drains once every workgroup has been dispatched and returned; a bounded
   // wait turns a launch that cannot drain into an error that says how far dispatch got
-  const double t0 = epoch_ms();
+  const double t0 = now_ms();
   for (;;) {
     const hipError_t e = hipStreamQuery(astream_);
     if (e == hipSuccess) break;
     if (e != hipErrorNotReady) hip_check(e, "asynchronous launch drain");
-    if (epoch_ms() - t0 > 30000.0) {
+    if (now_ms() - t0 > 30000.0) {
       unsigned c[32] = {0};
       (void)hipMemcpy(c, claim_ + 32 * ((launches_ - 1) & 1), sizeof(c), hipMemcpyDeviceToHost);
       std::string m = "LanesLoop: the asynchronous launch did not drain in 30 s; workgroups dispatched per XCD"

@@ -13,7 +13,9 @@
 //   real tracker and token queue with a scripted data plane,
 //   AsyncLanesProtocol (the host logic of LanesLoop::run_async / run_async_remote) over
 //   a real tracker, real windows, a real metrics sink and real token queues with a
-//   scripted plane (release records, tokens) and a scripted clock.
+//   scripted plane (release records, tokens) and a scripted clock,
+//   ShardFeed + RoundGate (the producer feed and the BSP round wait of the native loops)
+//   over real windows with a scripted clock.
 // Exit status 0 = all checks passed.
 #include <atomic>
 #include <chrono>
@@ -653,14 +655,13 @@ class LanesRig : public AsyncLanesPlane {
     for (int l = 0; l < L; ++l) {
       win.emplace_back(new SlidingWindow(1, 8, 100.0, 500, 16));
       cfg.window.push_back(reinterpret_cast<uintptr_t>(win.back().get()));
-      local_total.push_back(o.ds_rows > o.k[l] ? (o.ds_rows - o.k[l] + o.N - 1) / o.N : 0);
+      feeds.emplace_back(ShardFeed::Cfg{o.k[l], o.N, o.ds_rows, o.epochs, o.per_iter_rows, o.p_ms, cfg.window[l], 16,
+                                        lanes_api(), "LanesLoop: "});
     }
-    next_local.assign(L, 0);
-    seen_at_solve.assign(L, 0);
     last_.assign(L, RelRec{});
     inflight_.assign(L, 0);
     pull_left_.assign(L, 0);
-    p.bind(&cfg, 16, o.peer, this, &local_total, &next_local, &seen_at_solve, &times_);
+    p.bind(&cfg, o.peer, this, &feeds);
     g_trace = &trace_;
     g_rig = this;
   }
@@ -717,7 +718,7 @@ class LanesRig : public AsyncLanesPlane {
   std::unique_ptr<MetricsSink> sink;
   std::unique_ptr<CtrlQueue> ctrl, reply;
   std::vector<std::unique_ptr<SlidingWindow>> win;
-  std::vector<int64_t> local_total, next_local, seen_at_solve;
+  std::vector<ShardFeed> feeds;
   std::deque<Tok> script;
   double t_ms = 1000.0;         // the scripted wall clock
   double idle_step_ms = 1.0;    // ... advances by this on every look at an empty token slot
@@ -808,7 +809,6 @@ class LanesRig : public AsyncLanesPlane {
   }
   std::vector<EvalSlot> slots_;
   std::string qname_;
-  std::vector<double> times_;
   std::vector<std::string> trace_;
   std::string brief_;
   std::vector<RelRec> last_;
@@ -1218,6 +1218,281 @@ static void test_lanes_protocol() {
 }
 #undef R
 
+// ---- ShardFeed + RoundGate (shard_feed.h) ----
+// A feed over a real window (at most 8 rows in a ring of 16, its target stays at the
+// maximum) and a ring of 16 slots.  The standard shard must wrap: worker 1 of 2 over 11
+// rows reads dataset rows 1, 3, 5, 7, 9 (5 local rows).  take(): what one deliver() did,
+// as k<keep> (src_first,step,n,slot)...  The expected lines are what the four polls
+// (BspLoop, LanesLoop, KeyRangeLoop, AsyncLanesProtocol::poll_async) computed before they
+// became this class, written out by hand.
+struct FeedRig {
+  explicit FeedRig(int per_iter_rows, int64_t epochs, double p_ms = 0.0, int64_t ds_rows = 11,
+                   const HostApi* api = host_api(), const char* who = "LanesLoop: ")
+      : win(1, 8, 100.0, 500, 16),
+        feed(ShardFeed::Cfg{1, 2, ds_rows, epochs, per_iter_rows, p_ms, reinterpret_cast<uintptr_t>(&win), 16, api,
+                            who}) {}
+  int64_t deliver(double now_ms) {
+    return feed.deliver(
+        now_ms, [&](int64_t keep) { trace += "k" + std::to_string((long long)keep); },
+        [&](int64_t src_first, int64_t step, int64_t n, int64_t slot) {
+          trace += " (" + std::to_string((long long)src_first) + "," + std::to_string((long long)step) + "," +
+                   std::to_string((long long)n) + "," + std::to_string((long long)slot) + ")";
+        });
+  }
+  std::string take() {
+    std::string o;
+    o.swap(trace);
+    return o;
+  }
+  // the cursor and the window: next_local size start seen
+  std::string at() const {
+    const ShardFeed::Window v = feed.window();
+    return std::to_string((long long)feed.next_local()) + " " + std::to_string((long long)v.size) + " " +
+           std::to_string((long long)v.start) + " " + std::to_string((long long)v.seen);
+  }
+  SlidingWindow win;
+  ShardFeed feed;
+  std::string trace;
+};
+
+static void test_shard_feed() {
+  {  // a, b, c: 4 rows per delivery, 2 epochs of 5 rows -- inside the first epoch; across its end
+     // (two runs, the second from the shard's first row again); the last delivery cut at the limit
+    FeedRig g(4, 2);
+    CHECK(g.feed.local_total() == 5 && g.feed.cap() == 16 && !g.feed.exhausted() && g.at() == "0 0 0 0");
+    CHECK(g.deliver(7.0) == 4);
+    CHECK_TRACE(g, "k4 (1,2,4,0)");
+    CHECK(g.at() == "4 4 0 4");
+    CHECK(g.deliver(7.0) == 4);
+    CHECK_TRACE(g, "k4 (9,2,1,4) (1,2,3,5)");
+    CHECK(g.at() == "8 8 0 8" && !g.feed.exhausted());
+    CHECK(g.deliver(8.0) == 2);
+    CHECK_TRACE(g, "k2 (7,2,2,8)");
+    CHECK(g.at() == "10 8 2 10" && g.feed.exhausted());
+    CHECK(g.deliver(9.0) == 0);  // exhausted: nothing, not even the keep hook
+    CHECK_TRACE(g, "");
+    CHECK(g.at() == "10 8 2 10");
+  }
+  {  // d: a delivery larger than the ring -- 20 rows, the first 4 are never emitted (the ring
+     // would overwrite them), the first surviving row is local row 4 in slot (0 + 4) % 16; the
+     // last run wraps the ring (slots 15, 0, 1, 2, 3); 20 is what deliver() returns
+    FeedRig g(20, 10);
+    CHECK(g.deliver(1.0) == 20);
+    CHECK_TRACE(g, "k16 (9,2,1,4) (1,2,5,5) (1,2,5,10) (1,2,5,15)");
+    CHECK(g.at() == "20 8 12 20");
+  }
+  {  // e: the ring slot wraps inside a run (the third delivery's second run: slots 15, 0, 1)
+    FeedRig g(6, 100);
+    CHECK(g.deliver(1.0) == 6);
+    CHECK_TRACE(g, "k6 (1,2,5,0) (1,2,1,5)");
+    CHECK(g.at() == "6 6 0 6");
+    CHECK(g.deliver(1.0) == 6);
+    CHECK_TRACE(g, "k6 (3,2,4,6) (1,2,2,10)");
+    CHECK(g.at() == "12 8 4 12");
+    CHECK(g.deliver(1.0) == 6);
+    CHECK_TRACE(g, "k6 (5,2,3,12) (1,2,3,15)");
+    CHECK(g.at() == "18 8 10 18");
+  }
+  {  // f: the producer clock (2 rows per second after a burst of 128 rows per worker).  The small
+     // shard lies inside the burst: nothing is due before its arrival time 0, then the whole
+     // epoch -- and no more than the epoch in one call, though the next epoch is due as well
+    FeedRig g(0, 2, 500.0);
+    CHECK(g.deliver(-1.0) == 0);
+    CHECK_TRACE(g, "");
+    CHECK(g.at() == "0 0 0 0");
+    CHECK(host_api()->due_rows(1, 2, 500.0, 11, 0, 0.0, 10, nullptr) == 5);
+    CHECK(g.deliver(0.0) == 5);
+    CHECK_TRACE(g, "k5 (1,2,5,0)");
+    CHECK(g.at() == "5 5 0 5");
+    CHECK(g.deliver(0.0) == 5);
+    CHECK_TRACE(g, "k5 (1,2,5,5)");
+    CHECK(g.at() == "10 8 2 10" && g.feed.exhausted());
+    // 300 local rows: the burst (local rows 0..127) at 0 -- more than the ring holds --, local
+    // row 128 (dataset row 257) at 1000 ms, row 129 at 2000 ms, row 130 at 3000 ms
+    FeedRig h(0, 1, 500.0, 600);
+    CHECK(h.feed.local_total() == 300);
+    CHECK(host_api()->due_rows(1, 2, 500.0, 600, 0, 0.0, 300, nullptr) == 128);
+    CHECK(h.deliver(0.0) == 128);
+    CHECK_TRACE(h, "k16 (225,2,16,0)");
+    CHECK(h.at() == "128 8 8 128");
+    CHECK(h.deliver(999.0) == 0);
+    CHECK_TRACE(h, "");
+    CHECK(host_api()->due_rows(1, 2, 500.0, 600, 128, 2000.0, 172, nullptr) == 2);
+    CHECK(h.deliver(2000.0) == 2);
+    CHECK_TRACE(h, "k2 (257,2,2,0)");
+    CHECK(h.at() == "130 8 10 130");
+  }
+  {  // g: a resume mid-epoch -- the window restored (3 rows, newest in slot 2), the cursor set
+    FeedRig g(4, 2);
+    g.win.restore(2, 3, 3);
+    g.feed.set_next_local(3);
+    CHECK(g.feed.next_local() == 3 && g.at() == "3 3 0 3");
+    CHECK(g.deliver(1.0) == 4);
+    CHECK_TRACE(g, "k4 (7,2,2,3) (1,2,2,5)");
+    CHECK(g.at() == "7 7 0 7");
+    g.feed.set_next_local(10);
+    CHECK(g.feed.exhausted() && g.deliver(1.0) == 0);
+    g.feed.set_seen_at_solve(5);
+    CHECK(g.feed.seen_at_solve() == 5);
+  }
+  {  // errors of the C ABI carry the loop's prefix; the cursor stays
+    static HostApi bad = [] {
+      HostApi x = *host_api();
+      x.window_insert_many = [](void*, const double*, int64_t) -> int64_t { return -1; };
+      x.last_error = []() -> const char* { return "boom"; };
+      return x;
+    }();
+    for (const char* who : {"BspLoop: ", "LanesLoop: ", "KeyRangeLoop: "}) {
+      FeedRig g(4, 2, 0.0, 11, &bad, who);
+      CHECK(error_of<std::runtime_error>([&] { g.deliver(1.0); }) == std::string(who) + "window insert: boom");
+      CHECK(g.feed.next_local() == 0 && g.take().empty());
+    }
+  }
+  {  // the cadence: new_rows 2, new_frac 0.5, new_cap 3, ramp 1 -- the first solves need
+     // max(2, min(ceil(size / 2), 3, 1 << solves)) new tuples; rows arrive one per delivery
+    LanesHostCfg c;
+    c.new_rows = 2;
+    c.new_frac = 0.5;
+    c.new_cap = 3;
+    c.new_ramp = 1;
+    FeedRig g(1, 4);
+    CHECK(!g.feed.solve_due(g.feed.window(), 0));  // no rows: never
+    // deliveries until solve 0, 1, ... is due: 2 of windows of 1-2 and 3-4 rows (new_rows), then
+    // ceil(size / 2) capped at 3 (new_cap; the ramp's 4 no longer binds)
+    const int want[] = {2, 2, 3, 3, 3};
+    const int64_t seen_then[] = {2, 4, 7, 10, 13};
+    for (int solve = 0; solve < 5; ++solve) {
+      int n = 0;
+      ShardFeed::Window v = g.feed.window();
+      CHECK(solve == 0 || !g.feed.solve_due(v, c.new_tuples_needed(v.size, solve)));
+      CHECK(solve == 0 || g.feed.solve_due(v, 0));  // (no cadence: at once)
+      while (!g.feed.solve_due(v, c.new_tuples_needed(v.size, solve)) && n < 10) {
+        g.deliver(1.0);
+        v = g.feed.window();
+        ++n;
+      }
+      CHECK(n == want[solve] && v.seen == seen_then[solve]);
+      g.feed.mark_solved(v.seen);
+      CHECK(g.feed.seen_at_solve() == v.seen);
+    }
+    CHECK(c.new_tuples_needed(8) == 3 && c.new_tuples_needed(8, 0) == 2 && c.new_tuples_needed(8, 2) == 3);
+    // a stream that ended solves on what it has
+    ShardFeed::Window v = g.feed.window();
+    CHECK(!g.feed.solve_due(v, 3));
+    g.feed.set_next_local(20);
+    CHECK(g.feed.exhausted() && g.feed.solve_due(v, 3));
+  }
+}
+
+struct GateClock : HostClock {
+  double now_ms() override { return t_ms; }
+  int64_t mono_ns() override { return 0; }
+  void idle_sleep(int us) override {
+    ++sleeps;
+    slept_us += us;
+    t_ms += sleep_step_ms >= 0.0 ? sleep_step_ms : us / 1000.0;
+  }
+  double t_ms = 999.0;
+  double sleep_step_ms = -1.0;  // the clock advances by this per sleep (< 0: the sleep's length)
+  int sleeps = 0;
+  int64_t slept_us = 0;
+};
+
+static void test_round_gate() {
+  const char* const starved[] = {"BspLoop: no rows for 600 s", "LanesLoop: no rows for a worker",
+                                 "KeyRangeLoop: no rows"};
+  // the caller's hook: deliver for every lane, as the loops do; the times it was given
+  std::vector<double> nows;
+  auto deliver_all = [&](std::vector<FeedRig*> rigs) {
+    return [&nows, rigs](double now) {
+      nows.push_back(now);
+      for (FeedRig* g : rigs) g->deliver(now);
+    };
+  };
+  {  // ready at once: one delivery at the time since t0, no sleep, the window handed back
+    GateClock clk;
+    FeedRig g(4, 2);
+    ShardFeed::Window v;
+    const RoundGate gate{&clk, 900.0, 600.0, starved[0]};
+    CHECK(gate.wait(&g.feed, 1, &v, deliver_all({&g})));
+    CHECK(clk.sleeps == 0 && nows == std::vector<double>({99.0}));
+    CHECK(v.size == 4 && v.start == 0 && v.seen == 4);
+    CHECK_TRACE(g, "k4 (1,2,4,0)");
+  }
+  {  // waits for rows: the producer (clock mode) starts at 1000 ms, the round at 999 ms -- two
+     // sleeps of 500 us, a delivery per try, ready on the third
+    GateClock clk;
+    FeedRig g(0, 2, 500.0);
+    ShardFeed::Window v;
+    nows.clear();
+    const RoundGate gate{&clk, 1000.0, 600.0, starved[0]};
+    CHECK(gate.wait(&g.feed, 1, &v, deliver_all({&g})));
+    CHECK(clk.sleeps == 2 && clk.slept_us == 1000 && nows == std::vector<double>({-1.0, -0.5, 0.0}));
+    CHECK(v.size == 5 && v.start == 0 && v.seen == 5);
+    CHECK_TRACE(g, "k5 (1,2,5,0)");
+  }
+  {  // two lanes: lane 1's stream ended and its window is empty -- the run ends at once, lane 0's
+     // rows of this try delivered (the caller flushes them)
+    GateClock clk;
+    FeedRig g0(4, 2), g1(4, 2);
+    g1.feed.set_next_local(10);
+    ShardFeed feeds[2] = {g0.feed, g1.feed};
+    ShardFeed::Window v[2];
+    int tries = 0;
+    const RoundGate gate{&clk, 0.0, 600.0, starved[1]};
+    CHECK(!gate.wait(feeds, 2, v, [&](double) {
+      ++tries;
+      for (ShardFeed& f : feeds) f.deliver(1.0, [](int64_t, int64_t, int64_t, int64_t) {});
+    }));
+    CHECK(tries == 1 && clk.sleeps == 0 && v[0].size == 4 && v[1].size == 0 && feeds[0].next_local() == 4);
+    // ... but an ended stream whose window still has rows goes on solving
+    g1.win.restore(2, 3, 3);
+    CHECK(gate.wait(feeds, 2, v, [](double) {}) && v[1].size == 3 && v[1].seen == 3);
+  }
+  {  // the deadline: nothing is due (the producer starts at 5000 ms); the round that still waits
+     // at 1000 ms is not run -- two sleeps from 999 ms
+    GateClock clk;
+    FeedRig g(0, 2, 500.0);
+    ShardFeed::Window v;
+    nows.clear();
+    const RoundGate gate{&clk, 5000.0, 600.0, starved[1], 1000.0};
+    CHECK(!gate.wait(&g.feed, 1, &v, deliver_all({&g})));
+    CHECK(clk.sleeps == 2 && clk.t_ms == 1000.0 && nows.size() == 3 && v.size == 0);
+    // no deadline (0): the same wait runs into the row timeout instead, below
+  }
+  for (const char* msg : starved) {  // no rows for longer than the budget (2 ms): the caller's message,
+                                     // after the tries at 999, 999.5, ... 1001 ms (5 sleeps)
+    GateClock clk;
+    FeedRig g(0, 2, 500.0);
+    ShardFeed::Window v;
+    const RoundGate gate{&clk, 5000.0, 0.002, msg};
+    CHECK(error_of<std::runtime_error>([&] { gate.wait(&g.feed, 1, &v, deliver_all({&g})); }) == msg);
+    CHECK(clk.sleeps == 5 && clk.t_ms == 1001.5);
+  }
+  {  // the cadence alone holds the round back far beyond the row budget (2 ms): no timeout.  128
+     // rows at 0, one more at 1000 ms and at 2000 ms; the round needs 130 tuples; the scripted
+     // sleep takes 500 ms
+    GateClock clk;
+    clk.t_ms = 1000.0;
+    clk.sleep_step_ms = 500.0;
+    FeedRig g(0, 1, 500.0, 600);
+    ShardFeed::Window v;
+    nows.clear();
+    int64_t asked = 0;
+    const RoundGate gate{&clk, 1000.0, 0.002, starved[1]};
+    CHECK(gate.wait(&g.feed, 1, &v, deliver_all({&g}), [&](int64_t size) {
+      asked = size;
+      return int64_t(130);
+    }));
+    CHECK(clk.sleeps == 4 && nows == std::vector<double>({0.0, 500.0, 1000.0, 1500.0, 2000.0}));
+    CHECK(asked == 8 && v.size == 8 && v.seen == 130 && g.feed.next_local() == 130);
+    CHECK_TRACE(g, "k16 (225,2,16,0)k1 (257,2,1,0)k1 (259,2,1,1)");
+    // the next round counts from this solve: 130 seen, none new
+    g.feed.mark_solved(v.seen);
+    CHECK(!g.feed.solve_due(g.feed.window(), 1) && g.feed.solve_due(g.feed.window(), 0));
+  }
+}
+
 int main() {
   test_tracker();
   test_tracker_faults();
@@ -1228,6 +1503,8 @@ int main() {
   test_metrics_sink();
   test_server_protocol();
   test_lanes_protocol();
+  test_shard_feed();
+  test_round_gate();
   if (g_fail) {
     std::fprintf(stderr, "%d check(s) failed\n", g_fail);
     return 1;

@@ -162,17 +162,12 @@ def test_riding_eval_matches_separate_launches(cuda, monkeypatch, N):
     assert len(res[0][2]) == 10 * N and res[0][2] == res[1][2]
 
 
-def test_native_bsp_loop_matches_python_loop(cuda, monkeypatch):
-    """The native BSP round loop (csrc/runtime/bsp_loop.h) logs exactly the rows of
-    the Python loop, ends at the same model, producer cursor, window and tracker."""
+def _native_bsp_vs_python(cuda, monkeypatch, train, test, rounds, **kw):
     monkeypatch.setenv("PSX_NATIVE_LANES", "0")  # (the single-worker loop; the lanes loop has its own tests)
-    train, test = synth_finefood(8000, seed=0), synth_finefood(1000, seed=1)
-    kw = dict(num_workers=1, max_iters=25, init="random", min_buffer_size=256, max_buffer_size=256,
-              rows_per_iter=96)
     res = []
     for native in ("1", "0"):
         monkeypatch.setenv("PSX_NATIVE_BSP", native)
-        eng = LocalEngine(_cfg(**kw), cuda, train=train, test=test)
+        eng = LocalEngine(_cfg(num_workers=1, max_iters=rounds, init="random", **kw), cuda, train=train, test=test)
         assert eng._native_bsp_ok() == (native == "1")
         out = eng.run()
         assert out.get("native_loop", False) == (native == "1")
@@ -184,9 +179,28 @@ def test_native_bsp_loop_matches_python_loop(cuda, monkeypatch):
                     (wk.source.next_local, wk.window.size, wk.window.start, wk.tuples_seen, wk.vc, wk.iters,
                      eng.server.updates, eng.server.tracker.min_clock())))
     assert torch.equal(res[0][0], res[1][0])
-    assert res[0][1] == res[1][1] and [r[0] for r in res[0][1]] == list(range(25))
-    assert res[0][2] == res[1][2] and len(res[0][2]) == 25
+    assert res[0][1] == res[1][1] and [r[0] for r in res[0][1]] == list(range(rounds))
+    assert res[0][2] == res[1][2] and len(res[0][2]) == rounds
     assert res[0][3] == res[1][3]
+    return res[0][3]
+
+
+def test_native_bsp_loop_matches_python_loop(cuda, monkeypatch):
+    """The native BSP round loop (csrc/runtime/bsp_loop.h) logs exactly the rows of
+    the Python loop, ends at the same model, producer cursor, window and tracker."""
+    train, test = synth_finefood(8000, seed=0), synth_finefood(1000, seed=1)
+    _native_bsp_vs_python(cuda, monkeypatch, train, test, 25, min_buffer_size=256, max_buffer_size=256,
+                          rows_per_iter=96)
+
+
+def test_native_bsp_loop_epoch_wrap_matches_python_loop(cuda, monkeypatch):
+    """Deliveries that wrap the shard's epoch (300 rows, 128 per round: rounds 2 and 4 deliver two
+    runs, the first by a ring-ingest launch, the last fused into the solve): bit for bit the
+    Python loop, the cursor at 6 x 128 rows."""
+    train, test = synth_finefood(300, seed=0), synth_finefood(200, seed=1)
+    end = _native_bsp_vs_python(cuda, monkeypatch, train, test, 6, min_buffer_size=256, max_buffer_size=256,
+                                rows_per_iter=128, epochs=4)
+    assert end[0] == 768 and end[3] == 768
 
 
 def test_native_bsp_loop_producer_clock(cuda):
