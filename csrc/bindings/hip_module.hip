@@ -19,6 +19,7 @@
 #include "../runtime/peer_server.h"
 #include "../runtime/keyrange_loop.h"
 #include "../kernels/lr_kernels.h"
+#include "../kernels/score_kernels.h"
 #include "../solver/solver.h"
 #include "../solver/wide_solver.h"
 
@@ -296,6 +297,26 @@ PYBIND11_MODULE(_psx_hip, m) {
                   P<float>(out), S(stream));
     hip_check(hipGetLastError(), "logits launch");
   });
+  // Scoring (psx/ops/score.py): per-row predictions (+ probabilities / losses when
+  // their pointers are given) and, with labels, the confusion counts conf [256] and
+  // the out-of-range label count oor [1] (both accumulated).
+  m.def(
+      "score",
+      [](int FP, int K, uintptr_t X, uintptr_t y, int T, uintptr_t whi, uintptr_t wlo, uintptr_t b, uintptr_t pred,
+         uintptr_t proba, uintptr_t nll, uintptr_t conf, uintptr_t oor, uintptr_t stream) {
+        if (!fp_supported(FP) || K < 2 || K > 16) throw std::invalid_argument("score: unsupported FP or K");
+        if (!pred) throw std::invalid_argument("score: null prediction buffer");
+        if (y && (!conf || !oor)) throw std::invalid_argument("score: labels need the count buffers");
+        if (nll && !y) throw std::invalid_argument("score: the per-row loss needs labels");
+        prepare_score_kernels();
+        const ScoreOut o{P<int32_t>(pred), P<float>(proba), P<float>(nll), P<int>(conf), P<int>(oor)};
+        launch_score(FP, K, P<const uint16_t>(X), P<const int32_t>(y), T, P<const uint16_t>(whi),
+                     P<const uint16_t>(wlo), P<const float>(b), o, S(stream));
+        hip_check(hipGetLastError(), "score launch");
+      },
+      py::arg("FP"), py::arg("K"), py::arg("X"), py::arg("y"), py::arg("T"), py::arg("whi"), py::arg("wlo"),
+      py::arg("b"), py::arg("pred"), py::arg("proba") = 0, py::arg("nll") = 0, py::arg("conf") = 0,
+      py::arg("oor") = 0, py::arg("stream") = 0);
   m.def(
       "server_apply",
       [](int K, int F, int FP, uintptr_t w, uintptr_t delta, float lr, uintptr_t whi, uintptr_t wlo, uintptr_t b,
@@ -584,6 +605,23 @@ PYBIND11_MODULE(_psx_hip, m) {
                        P<const float>(w), P<float>(out), S(stream));
     hip_check(hipGetLastError(), "wide_logits launch");
   });
+  m.def(
+      "wide_score",
+      [](int K, int KP, int64_t F, uintptr_t indptr, uintptr_t idx, uintptr_t val, uintptr_t y, int T, uintptr_t w,
+         uintptr_t pred, uintptr_t proba, uintptr_t nll, uintptr_t conf, uintptr_t oor, uintptr_t stream) {
+        if (K < 1 || K > KP || (KP != 1 && KP != 2 && KP != 4 && KP != 8 && KP != 16))
+          throw std::invalid_argument("wide_score: unsupported K / KP");
+        if (!pred) throw std::invalid_argument("wide_score: null prediction buffer");
+        if (y && (!conf || !oor)) throw std::invalid_argument("wide_score: labels need the count buffers");
+        if (nll && !y) throw std::invalid_argument("wide_score: the per-row loss needs labels");
+        const ScoreOut o{P<int32_t>(pred), P<float>(proba), P<float>(nll), P<int>(conf), P<int>(oor)};
+        launch_wide_score(K, KP, F, P<const int64_t>(indptr), P<const int32_t>(idx), P<const uint16_t>(val),
+                          P<const int32_t>(y), T, P<const float>(w), o, S(stream));
+        hip_check(hipGetLastError(), "wide_score launch");
+      },
+      py::arg("K"), py::arg("KP"), py::arg("F"), py::arg("indptr"), py::arg("idx"), py::arg("val"), py::arg("y"),
+      py::arg("T"), py::arg("w"), py::arg("pred"), py::arg("proba") = 0, py::arg("nll") = 0, py::arg("conf") = 0,
+      py::arg("oor") = 0, py::arg("stream") = 0);
   m.def("wide_apply_sparse", [](uintptr_t w, int64_t F, int KP, uintptr_t U_dev, int U_host, uintptr_t uniq,
                                 uintptr_t dloc, float lr, int umax, uintptr_t stream) {
     launch_wide_apply_sparse(P<float>(w), F, KP, P<const unsigned>(U_dev), U_host, P<const int32_t>(uniq),

@@ -9,6 +9,7 @@
 
 #include "common.h"
 #include "wide_kernels.h"
+#include "wide_row.h"
 
 namespace psx {
 
@@ -18,26 +19,6 @@ typedef __attribute__((address_space(1))) unsigned long long gu64w;
 
 __device__ __forceinline__ double ld_agent_f64(const double* p) {
   return __builtin_bit_cast(double, __hip_atomic_load((gu64w*)p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT));
-}
-
-template <int KP>
-__device__ __forceinline__ void ldk(const float* __restrict__ p, float (&o)[KP]) {
-  if constexpr (KP % 4 == 0) {
-#pragma unroll
-    for (int q = 0; q < KP / 4; ++q) {
-      const f32x4 t = *(const f32x4*)(p + 4 * q);
-      o[4 * q] = t[0];
-      o[4 * q + 1] = t[1];
-      o[4 * q + 2] = t[2];
-      o[4 * q + 3] = t[3];
-    }
-  } else if constexpr (KP == 2) {
-    const float2 t = *(const float2*)p;
-    o[0] = t.x;
-    o[1] = t.y;
-  } else {
-    o[0] = p[0];
-  }
 }
 
 // Class probabilities -> residual r = (p - onehot(y)) * invB and the row loss.
@@ -1397,30 +1378,6 @@ void launch_sparse_ring_ingest_many(const int64_t* indptr, const int32_t* idx, c
 // ---------------------------------------------------------------------------
 // Test-set evaluation: one wavefront per row, LDS confusion counts, last
 // workgroup publishes into the pinned EvalSlot (protocol of test_eval_kernel).
-template <int KP>
-__device__ __forceinline__ void wide_row_margins(int64_t F, const int64_t* __restrict__ indptr,
-                                                 const int32_t* __restrict__ idx, const uint16_t* __restrict__ val,
-                                                 int64_t row, const float* __restrict__ w, float (&z)[KP]) {
-  const int lane = threadIdx.x & 63;
-#pragma unroll
-  for (int k = 0; k < KP; ++k) z[k] = 0.f;
-  const int64_t a = indptr[row], b = indptr[row + 1];
-  for (int64_t e = a + lane; e < b; e += 64) {
-    const int f = idx[e];
-    const float v = bf2f(val[e]);
-    float wv[KP];
-    ldk<KP>(w + (int64_t)f * KP, wv);
-#pragma unroll
-    for (int k = 0; k < KP; ++k) z[k] += v * wv[k];
-  }
-#pragma unroll
-  for (int k = 0; k < KP; ++k) z[k] = wave_sum(z[k]);
-  float bv[KP];
-  ldk<KP>(w + F * KP, bv);
-#pragma unroll
-  for (int k = 0; k < KP; ++k) z[k] += bv[k];
-}
-
 // Margins of up to 4 rows per wave for the evaluation: 16 lanes per row, each
 // lane with 4 entries' loads in flight (ids/values, then the local-model map,
 // then the weight rows), so a wave keeps 4 rows x 64 gathers outstanding
@@ -1499,20 +1456,6 @@ __device__ __forceinline__ void wide_rows4_margins(int64_t F, const int64_t* __r
 #pragma unroll
     for (int k = 0; k < KP; ++k) zb[k] += bv[k];
   }
-}
-
-template <int KP>
-__device__ __forceinline__ int wide_argmax(int K, const float (&z)[KP]) {
-  if (K == 1) return z[0] > 0.f ? 1 : 0;
-  int best = 0;
-  float bz = -INFINITY;
-#pragma unroll
-  for (int k = 0; k < KP; ++k)
-    if (k < K && z[k] > bz) {
-      bz = z[k];
-      best = k;
-    }
-  return best;
 }
 
 // Paired mode (slot2 != nullptr, needs the overlay): row 1 = the overlay model
