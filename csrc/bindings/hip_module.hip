@@ -20,6 +20,7 @@
 #include "../runtime/keyrange_loop.h"
 #include "../kernels/lr_kernels.h"
 #include "../kernels/score_kernels.h"
+#include "../solver/fit.h"
 #include "../solver/solver.h"
 #include "../solver/wide_solver.h"
 
@@ -317,6 +318,60 @@ PYBIND11_MODULE(_psx_hip, m) {
       py::arg("FP"), py::arg("K"), py::arg("X"), py::arg("y"), py::arg("T"), py::arg("whi"), py::arg("wlo"),
       py::arg("b"), py::arg("pred"), py::arg("proba") = 0, py::arg("nll") = 0, py::arg("conf") = 0,
       py::arg("oor") = 0, py::arg("stream") = 0);
+  // Full-batch trainer (psx/ops/fit.py): the host loop of a fit runs with the GIL released.
+  py::class_<BatchFitter>(m, "BatchFitter")
+      .def(py::init<int, int, int, int, int>(), py::arg("K"), py::arg("F"), py::arg("FP"), py::arg("hist") = 10,
+           py::arg("max_wg") = 0)
+      .def(
+          "set_data",
+          [](BatchFitter& f, uintptr_t X, uintptr_t y, int64_t N, int64_t Npad, uintptr_t stream) {
+            f.set_data(P<const uint16_t>(X), P<const int32_t>(y), N, Npad, S(stream));
+          },
+          py::arg("X"), py::arg("y"), py::arg("N"), py::arg("Npad"), py::arg("stream") = 0)
+      .def(
+          "loss_grad",
+          [](BatchFitter& f, uintptr_t w, uintptr_t grad, uintptr_t stream) {
+            return f.loss_grad(P<const float>(w), P<float>(grad), S(stream));
+          },
+          py::arg("w"), py::arg("grad"), py::arg("stream") = 0)
+      .def(
+          "begin",
+          [](BatchFitter& f, uintptr_t w0, int max_iter, double tol, double reg_param, int ls_max, bool zero_const,
+             uintptr_t stream) {
+            FitOpts o;
+            o.max_iter = max_iter;
+            o.tol = tol;
+            o.reg_param = reg_param;
+            o.ls_max = ls_max;
+            o.zero_const = zero_const ? 1 : 0;
+            f.begin(P<const float>(w0), o, S(stream));
+          },
+          py::arg("w0"), py::arg("max_iter"), py::arg("tol"), py::arg("reg_param"), py::arg("ls_max"),
+          py::arg("zero_const") = true, py::arg("stream") = 0)
+      .def(
+          "run",
+          [](BatchFitter& f, int max_accept, uintptr_t stream) {
+            py::gil_scoped_release nogil;
+            return f.run(max_accept, S(stream));
+          },
+          py::arg("max_accept"), py::arg("stream") = 0)
+      .def(
+          "current", [](BatchFitter& f, uintptr_t w_out, uintptr_t stream) { f.current(P<float>(w_out), S(stream)); },
+          py::arg("w_out"), py::arg("stream") = 0)
+      .def(
+          "read_std", [](BatchFitter& f, uintptr_t out, uintptr_t stream) { f.read_std(P<float>(out), S(stream)); },
+          py::arg("out"), py::arg("stream") = 0)
+      .def_property_readonly("done", &BatchFitter::done)
+      .def_property_readonly("reason", &BatchFitter::reason)
+      .def_property_readonly("evals", &BatchFitter::evals)
+      .def_property_readonly("accepted", &BatchFitter::accepted)
+      .def_property_readonly("ls_fail", &BatchFitter::ls_fail)
+      .def_property_readonly("dir_reset", &BatchFitter::dir_reset)
+      .def_property_readonly("objective", &BatchFitter::objective)
+      .def_property_readonly("log_loss", &BatchFitter::log_loss)
+      .def_property_readonly("history", &BatchFitter::history)
+      .def_property_readonly("eval_seconds", &BatchFitter::eval_seconds)
+      .def_property_readonly("grid", &BatchFitter::grid);
   m.def(
       "server_apply",
       [](int K, int F, int FP, uintptr_t w, uintptr_t delta, float lr, uintptr_t whi, uintptr_t wlo, uintptr_t b,

@@ -277,3 +277,186 @@ def local_solve_reference(
 
 def predict(X: torch.Tensor, coef: torch.Tensor, intercept: torch.Tensor) -> torch.Tensor:
     return (X.float() @ coef.float().t() + intercept.float()).argmax(1)
+
+
+# ---------------------------------------------------------------------------
+# Full-batch fit (oracle of psx/ops/fit.py and csrc/kernels/fit_kernels.hip)
+@dataclass
+class FitReference:
+    coef: torch.Tensor  # [K, F] float64, original feature space
+    intercept: torch.Tensor  # [K] float64, centred
+    std: torch.Tensor  # [F] float64 sample std of the features (0: excluded)
+    objective: float  # f at the result
+    log_loss: float  # its unregularised part
+    history: list  # objective at the start and after every accepted iteration
+    iters: int
+    evals: int
+    ls_fail: int
+    reason: str  # tol | max_iter | line_search | no_descent
+
+
+def fit_reference(
+    X: torch.Tensor,
+    y: torch.Tensor,
+    coef0: torch.Tensor | None = None,
+    intercept0: torch.Tensor | None = None,
+    *,
+    num_classes: int | None = None,
+    reg_param: float = 0.0,
+    max_iter: int = 100,
+    tol: float = 1e-6,
+    hist: int = 10,
+    ls_max: int = 20,
+    zero_const: bool = True,
+) -> FitReference:
+    """Fit to convergence: Spark's ``LogisticRegression.fit`` with
+    ``standardization=true``, ``elasticNetParam=0``.
+
+    ``f(beta, b) = mean cross entropy + 0.5 * reg_param * sum(beta^2)`` with
+    ``beta = coef * sigma`` (sigma the sample std; a feature with sigma 0 is excluded),
+    intercepts unpenalised.  The optimiser is :func:`local_solve_reference`'s -- the
+    same L-BFGS, strong-Wolfe line search and stopping tests, float64 -- without the
+    slot budget, with the L2 term, a per-iteration objective history and a
+    termination reason.  Intercepts are always centred over the classes, coefficients
+    only when ``reg_param == 0`` (with a penalty the optimum is centred by itself)."""
+    X = X.double()
+    y = y.long()
+    if coef0 is None:
+        if num_classes is None:
+            raise ValueError("fit_reference needs num_classes or a start")
+        coef0 = torch.zeros(num_classes, X.shape[1], dtype=torch.float64)
+    K, F = coef0.shape
+    w_old = coef0.double()
+    b_old = torch.zeros(K, dtype=torch.float64) if intercept0 is None else intercept0.double()
+    lam = float(reg_param)
+    sd = feature_std(X)
+    live = sd > 0
+    inv = torch.where(live, 1.0 / torch.where(live, sd, torch.ones_like(sd)), torch.zeros_like(sd))
+    wfix = torch.zeros_like(w_old) if zero_const else torch.where(live, torch.zeros_like(w_old), w_old)
+    last = {}
+
+    def fg(v):
+        c, b = v[: K * F].view(K, F), v[K * F :]
+        loss, gc, gb = multinomial_loss_grad(X, y, c * inv + wfix, b)
+        f, g = float(loss), torch.cat([(gc * inv).reshape(-1), gb])
+        last["loss"] = f
+        if lam != 0.0:
+            f = f + 0.5 * lam * float((c * c).sum())
+            g = g + lam * torch.cat([c.reshape(-1), torch.zeros(K, dtype=torch.float64)])
+        return f, g
+
+    x = torch.cat([(w_old * sd).reshape(-1), b_old])
+    f_c, g_c = fg(x)
+    log_loss = last["loss"]
+    evals, it, ls_fail = 1, 0, 0
+    history = [f_c]
+    S, Yh = [], []
+    gnorm = float(g_c.norm())
+    if not math.isfinite(f_c):
+        reason = "no_descent"
+    elif max_iter <= 0:
+        reason = "max_iter"
+    elif gnorm == 0:
+        reason = "tol"
+    else:
+        reason = None
+        d = -g_c.clone()
+        dg0 = float(g_c @ d)
+        t = 1.0 / gnorm
+    while reason is None:
+        lo, hi, zoom, ls_i, accepted_t = (0.0, f_c, dg0), None, False, 0, None
+        while True:  # one strong-Wolfe line search
+            f_t, g_t = fg(x + t * d)
+            evals += 1
+            dd = float(g_t @ d)
+            ls_i += 1
+            finite = math.isfinite(f_t)
+            armijo = finite and f_t <= f_c + 1e-4 * t * dg0
+            tn = t
+            if not zoom:
+                if not finite:
+                    tn = t * 0.5
+                elif (not armijo) or (f_t >= lo[1] and ls_i > 1):
+                    hi, zoom = (t, f_t, dd), True
+                    tn = _interp(*lo, *hi)
+                elif abs(dd) <= 0.9 * abs(dg0):
+                    accepted_t = t
+                    break
+                elif dd >= 0:
+                    hi, lo, zoom = lo, (t, f_t, dd), True
+                    tn = _interp(*lo, *hi)
+                else:
+                    lo = (t, f_t, dd)
+                    tn = t * 1.5
+            else:
+                if (not armijo) or f_t >= lo[1]:
+                    hi = (t, f_t, dd)
+                else:
+                    if abs(dd) <= 0.9 * abs(dg0):
+                        accepted_t = t
+                        break
+                    if dd * (hi[0] - lo[0]) >= 0:
+                        hi = lo
+                    lo = (t, f_t, dd)
+                tn = _interp(*lo, *hi)
+            if ls_i >= ls_max:
+                ls_fail += 1
+                if armijo and f_t < f_c:
+                    accepted_t = t  # settle for sufficient decrease
+                else:
+                    reason = "line_search" if finite else "no_descent"
+                break
+            t = tn
+        if accepted_t is None:
+            break
+        t = accepted_t
+        s_new = t * d
+        y_new = g_t - g_c
+        x = x + s_new
+        it += 1
+        f_prev, f_c = f_c, f_t
+        log_loss = last["loss"]
+        history.append(f_c)
+        fscale = max(abs(f_t), 1.0)
+        if it >= max_iter:
+            reason = "max_iter"
+            break
+        if float(g_t.norm()) <= tol * fscale or abs(f_prev - f_t) <= tol * fscale:
+            reason = "tol"
+            break
+        g_c = g_t
+        sy, yy = float(s_new @ y_new), float(y_new @ y_new)
+        if sy > 1e-10 * (yy if yy > 0 else 1.0) and yy > 0:
+            S.append(s_new)
+            Yh.append(y_new)
+            if len(S) > hist:
+                S.pop(0)
+                Yh.pop(0)
+        if S:  # two-loop recursion
+            q = g_c.clone()
+            alphas = []
+            for s_i, y_i in zip(reversed(S), reversed(Yh)):
+                rho = 1.0 / float(s_i @ y_i)
+                a = rho * float(s_i @ q)
+                alphas.append((rho, a))
+                q -= a * y_i
+            r = (float(S[-1] @ Yh[-1]) / float(Yh[-1] @ Yh[-1])) * q
+            for (s_i, y_i), (rho, a) in zip(zip(S, Yh), reversed(alphas)):
+                r += s_i * (a - rho * float(y_i @ r))
+            d = -r
+        else:
+            d = -g_c
+        dg0 = float(g_c @ d)
+        if not dg0 < 0:
+            S.clear()
+            Yh.clear()
+            d = -g_c
+            dg0 = float(g_c @ d)
+        t = 1.0
+    c, b = x[: K * F].view(K, F), x[K * F :]
+    coef = torch.where(live, c * inv, wfix)
+    if lam == 0.0:
+        coef = coef - coef.mean(0, keepdim=True)
+    b = b - b.mean()
+    return FitReference(coef=coef, intercept=b, std=sd, objective=f_c, log_loss=log_loss, history=history, iters=it,
+                        evals=evals, ls_fail=ls_fail, reason=reason)

@@ -12,6 +12,11 @@ and reports the ceiling the streaming runs approach.
 Usage:
   python tools/ground_truth.py --train data/train.csv --test data/test.csv
   python tools/ground_truth.py --synthetic [--rows 90000 --test_rows 4877]
+  python tools/ground_truth.py --synthetic --fitter psx [--device cuda:0] [--timing]
+
+``--fitter torch`` (the default) is the float64 torch L-BFGS below; ``--fitter psx`` is
+the project's own full-batch trainer (psx/ops/fit.py: the HIP kernels on a GPU, the
+float64 oracle on the CPU), whose ``reg_param`` is ``--l2`` and ``max_iter`` ``--iters``.
 """
 from __future__ import annotations
 
@@ -19,6 +24,7 @@ import argparse
 import json
 import os
 import sys
+import time
 
 import numpy as np
 import torch
@@ -55,6 +61,19 @@ def fit_full_batch(X: torch.Tensor, y: torch.Tensor, K: int, l2: float = 0.0, it
     return coef, inter, float(loss)
 
 
+def fit_full_batch_psx(ds, K: int, l2: float = 0.0, iters: int = 200, device=None):
+    """The same fit through psx.ops.fit.BatchFitter; ``ds`` is a Dataset.  Returns float64
+    (coef [K, F], intercepts [K], objective) like fit_full_batch."""
+    from psx.models.logreg import ModelSpec
+    from psx.ops.fit import BatchFitter, FitOptions
+
+    device = device or ("cuda:0" if torch.cuda.is_available() else "cpu")
+    spec = ModelSpec(ds.num_features, K)
+    res = BatchFitter(spec, device, FitOptions(max_iter=iters, reg_param=l2)).fit(ds)
+    w = res.w.cpu()
+    return spec.coef(w).double(), spec.intercept(w).double(), float(res.objective)
+
+
 def main(argv=None) -> int:
     ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
     ap.add_argument("--train", default=None)
@@ -65,6 +84,9 @@ def main(argv=None) -> int:
     ap.add_argument("--features", type=int, default=1024)
     ap.add_argument("--l2", type=float, default=0.0)
     ap.add_argument("--iters", type=int, default=200)
+    ap.add_argument("--fitter", default="torch", choices=["torch", "psx"])
+    ap.add_argument("--device", default=None, help="--fitter psx: cpu | cuda:N (default: cuda if available)")
+    ap.add_argument("--timing", action="store_true", help="add the fit's wall seconds to the output")
     a = ap.parse_args(argv)
     if a.synthetic or not a.train:
         tr = synth_finefood(a.rows, num_features=a.features, seed=0)
@@ -73,13 +95,20 @@ def main(argv=None) -> int:
         tr = load_csv(a.train)
         te = load_csv(a.test or a.train)
     K = int(max(int(tr.y.max()), int(te.y.max())) + 1)
-    coef, inter, loss = fit_full_batch(tr.float_features(), tr.y.long(), K, a.l2, a.iters)
+    t0 = time.perf_counter()
+    if a.fitter == "psx":
+        coef, inter, loss = fit_full_batch_psx(tr, K, a.l2, a.iters, a.device)
+    else:
+        coef, inter, loss = fit_full_batch(tr.float_features(), tr.y.long(), K, a.l2, a.iters)
+    dt = time.perf_counter() - t0
     pred = (te.float_features().double() @ coef.t() + inter).argmax(1)
     c = confusion(te.y.numpy(), pred.numpy(), K)
     f1, acc = metrics_from_confusion(c)
     out = {"train_rows": int(tr.rows), "test_rows": int(te.rows), "features": int(tr.num_features), "classes": K,
            "train_loss": round(loss, 6), "test_accuracy": round(acc, 4), "test_weighted_f1": round(f1, 4),
            "per_class_recall": np.round(np.diag(c) / np.maximum(c.sum(1), 1), 4).tolist()}
+    if a.timing:
+        out.update(fitter=a.fitter, fit_seconds=round(dt, 3))
     print(json.dumps(out))
     return 0
 

@@ -4,7 +4,7 @@ matched producer rates a streaming run is data-arrival bound, so its accuracy
 at time t is judged against this curve at n = tuples seen by t (the synthetic
 fine-food set is absent from the reference, whose curves are on the real data).
 
-    python tools/learning_curve.py [--ns 500,1000,...] [--out evaluation/learning_curve.json]
+    python tools/learning_curve.py [--ns 500,1000,...] [--out evaluation/learning_curve.json] [--fitter torch|psx]
 """
 import argparse
 import json
@@ -23,8 +23,11 @@ def main():
     ap.add_argument("--ns", default="500,1000,2000,3000,4000,6000,8000,12000,16000,24000,32000,90000")
     ap.add_argument("--out", default="evaluation/learning_curve.json")
     ap.add_argument("--threads", type=int, default=2)
+    ap.add_argument("--fitter", default="torch", choices=["torch", "psx"],
+                    help="torch: float64 L-BFGS on the CPU; psx: the project's full-batch trainer (psx/ops/fit.py)")
     a = ap.parse_args()
-    from ground_truth import fit_full_batch
+    from ground_truth import fit_full_batch, fit_full_batch_psx
+    from psx.utils.data import Dataset
     from psx.utils.data import FINEFOOD_TEST_ROWS, synth_finefood
     from psx.utils.metrics import confusion, metrics_from_confusion
 
@@ -33,7 +36,10 @@ def main():
     tr, te = synth_finefood(max(ns), seed=0), synth_finefood(FINEFOOD_TEST_ROWS, seed=1)
     rows = []
     for n in ns:
-        coef, inter, _ = fit_full_batch(tr.float_features()[:n], tr.y[:n].long(), 6, 0.0, 150)
+        if a.fitter == "psx":
+            coef, inter, _ = fit_full_batch_psx(Dataset(tr.X[:n], tr.y[:n], tr.num_features), 6, 0.0, 150)
+        else:
+            coef, inter, _ = fit_full_batch(tr.float_features()[:n], tr.y[:n].long(), 6, 0.0, 150)
         pred = (te.float_features().double() @ coef.t() + inter).argmax(1)
         f1, acc = metrics_from_confusion(confusion(te.y.numpy(), pred.numpy(), 6))
         rows.append({"tuples": n, "test_accuracy": round(acc, 4), "test_weighted_f1": round(f1, 4)})
