@@ -22,6 +22,7 @@
 #include "../kernels/score_kernels.h"
 #include "../solver/fit.h"
 #include "../solver/solver.h"
+#include "../solver/wide_fit.h"
 #include "../solver/wide_solver.h"
 
 namespace py = pybind11;
@@ -372,6 +373,95 @@ PYBIND11_MODULE(_psx_hip, m) {
       .def_property_readonly("history", &BatchFitter::history)
       .def_property_readonly("eval_seconds", &BatchFitter::eval_seconds)
       .def_property_readonly("grid", &BatchFitter::grid);
+  // Full-batch trainer of the wide model (psx/ops/wide_fit.py)
+  py::class_<WideBatchFitter>(m, "WideBatchFitter")
+      .def(py::init<int, int, int, int>(), py::arg("K"), py::arg("KP"), py::arg("hist") = 10, py::arg("max_wg") = 0)
+      .def(
+          "set_data",
+          [](WideBatchFitter& f, uintptr_t indptr, uintptr_t col, uintptr_t val, uintptr_t y, uintptr_t uniq,
+             uintptr_t colptr, uintptr_t crow, uintptr_t cval, uintptr_t item_begin, uintptr_t item_end,
+             uintptr_t col_item0, uintptr_t short_items, uintptr_t long_items, int64_t N, int64_t U, int64_t F,
+             int64_t n_items, int64_t n_short, int64_t n_long, uintptr_t stream) {
+            WideFitData d{};
+            d.indptr = P<const int64_t>(indptr);
+            d.col = P<const int32_t>(col);
+            d.val = P<const uint16_t>(val);
+            d.y = P<const int32_t>(y);
+            d.uniq = P<const int32_t>(uniq);
+            d.colptr = P<const int64_t>(colptr);
+            d.crow = P<const int32_t>(crow);
+            d.cval = P<const uint16_t>(cval);
+            d.item_begin = P<const int64_t>(item_begin);
+            d.item_end = P<const int64_t>(item_end);
+            d.col_item0 = P<const int32_t>(col_item0);
+            d.short_items = P<const int32_t>(short_items);
+            d.long_items = P<const int32_t>(long_items);
+            d.N = N;
+            d.U = U;
+            d.F = F;
+            d.n_items = n_items;
+            d.n_short = n_short;
+            d.n_long = n_long;
+            f.set_data(d, S(stream));
+          },
+          py::arg("indptr"), py::arg("col"), py::arg("val"), py::arg("y"), py::arg("uniq"), py::arg("colptr"),
+          py::arg("crow"), py::arg("cval"), py::arg("item_begin"), py::arg("item_end"), py::arg("col_item0"),
+          py::arg("short_items"), py::arg("long_items"), py::arg("N"), py::arg("U"), py::arg("F"),
+          py::arg("n_items"), py::arg("n_short"), py::arg("n_long"), py::arg("stream") = 0)
+      .def(
+          "loss_grad",
+          [](WideBatchFitter& f, uintptr_t w, uintptr_t grad, uintptr_t stream) {
+            return f.loss_grad(P<const float>(w), P<float>(grad), S(stream));
+          },
+          py::arg("w"), py::arg("grad"), py::arg("stream") = 0)
+      .def(
+          "begin",
+          [](WideBatchFitter& f, uintptr_t w0, int max_iter, double tol, double reg_param, int ls_max,
+             bool zero_const, uintptr_t stream) {
+            FitOpts o;
+            o.max_iter = max_iter;
+            o.tol = tol;
+            o.reg_param = reg_param;
+            o.ls_max = ls_max;
+            o.zero_const = zero_const ? 1 : 0;
+            f.begin(P<const float>(w0), o, S(stream));
+          },
+          py::arg("w0"), py::arg("max_iter"), py::arg("tol"), py::arg("reg_param"), py::arg("ls_max"),
+          py::arg("zero_const") = true, py::arg("stream") = 0)
+      .def(
+          "run",
+          [](WideBatchFitter& f, int max_accept, uintptr_t stream) {
+            py::gil_scoped_release nogil;
+            return f.run(max_accept, S(stream));
+          },
+          py::arg("max_accept"), py::arg("stream") = 0)
+      .def(
+          "current",
+          [](WideBatchFitter& f, uintptr_t w_out, uintptr_t stream) { f.current(P<float>(w_out), S(stream)); },
+          py::arg("w_out"), py::arg("stream") = 0)
+      .def(
+          "read_std",
+          [](WideBatchFitter& f, uintptr_t out, uintptr_t stream) { f.read_std(P<float>(out), S(stream)); },
+          py::arg("out"), py::arg("stream") = 0)
+      .def(
+          "stage_ms",
+          [](WideBatchFitter& f, bool raw, uintptr_t stream) {
+            py::gil_scoped_release nogil;
+            return f.stage_ms(raw ? 1 : 0, S(stream));
+          },
+          py::arg("raw"), py::arg("stream") = 0)
+      .def_property_readonly("done", &WideBatchFitter::done)
+      .def_property_readonly("reason", &WideBatchFitter::reason)
+      .def_property_readonly("evals", &WideBatchFitter::evals)
+      .def_property_readonly("accepted", &WideBatchFitter::accepted)
+      .def_property_readonly("ls_fail", &WideBatchFitter::ls_fail)
+      .def_property_readonly("dir_reset", &WideBatchFitter::dir_reset)
+      .def_property_readonly("objective", &WideBatchFitter::objective)
+      .def_property_readonly("log_loss", &WideBatchFitter::log_loss)
+      .def_property_readonly("history", &WideBatchFitter::history)
+      .def_property_readonly("eval_seconds", &WideBatchFitter::eval_seconds)
+      .def_property_readonly("grid", &WideBatchFitter::grid);
+  m.attr("wide_fit_short") = kWideFitShort;
   m.def(
       "server_apply",
       [](int K, int F, int FP, uintptr_t w, uintptr_t delta, float lr, uintptr_t whi, uintptr_t wlo, uintptr_t b,

@@ -18,6 +18,7 @@
 // order, butterflies): a fit is bit-reproducible.  No atomics at all.
 #include <hip/hip_runtime.h>
 
+#include "fit_body.h"
 #include "fit_kernels.h"
 #include "solve_body.h"
 
@@ -236,65 +237,17 @@ __global__ __launch_bounds__(256) void fit_reduce_kernel(FitDev dv, int nfw, dou
   if (l == 0) dp[3 + 2 * H] = v;
 }
 
-// One workgroup: the NB partial dots (4 strided lanes per value, combined in
-// order), the nfw loss partials, f_t.
+// One workgroup: f_t, the mean loss and the dots (fit_dots_body of fit_body.h).
 __global__ __launch_bounds__(256) void fit_dots_kernel(FitDev dv, int NB, int nfw, double reg, int raw) {
-  __shared__ double red[4][64];
-  __shared__ double lred[256];
-  const int t = threadIdx.x, k = t & 63, q = t >> 6;
-  const int nd = raw ? 0 : 3 + 2 * dv.H + 1;
-  double a = 0.0;
-  if (k < nd)
-    for (int b = q; b < NB; b += 4) a += dv.dpart[(size_t)b * kFitDotStride + k];
-  red[q][k] = a;
-  double ls = 0.0;
-  for (int g = t; g < nfw; g += 256) ls += (double)dv.part[(size_t)g * kPartStride + 16];
-  lred[t] = ls;
-  __syncthreads();
-  if (t < nd - 1) dv.out[kFitOutDots + t] = ((red[0][t] + red[1][t]) + red[2][t]) + red[3][t];
-  if (t == 0) {
-    double loss = 0.0;
-    for (int i = 0; i < 256; ++i) loss += lred[i];
-    loss /= (double)dv.N;
-    double bb = 0.0;
-    if (nd > 0) bb = ((red[0][nd - 1] + red[1][nd - 1]) + red[2][nd - 1]) + red[3][nd - 1];
-    dv.out[kFitOutF] = loss + 0.5 * reg * bb;
-    dv.out[kFitOutLoss] = loss;
-  }
+  fit_dots_body(dv.dpart, dv.part, dv.out, dv.H, dv.N, NB, nfw, reg, raw);
 }
 
 // ---------------------------------------------------------------------------
-// One controller action on the vectors.  x + t d is formed in fp64 and rounded
-// once, identically for the trial point and for the accepted iterate, so the
-// accepted x is exactly the point that was evaluated.
+// One controller action on the vectors (fit_update_body of fit_body.h).
 __global__ __launch_bounds__(256) void fit_update_kernel(FitDev dv, FitStep st) {
   const int e = blockIdx.x * 256 + threadIdx.x;
   if (e >= dv.n) return;
-  float x = dv.x[e], d = dv.d[e];
-  if (st.action == kActInit) {
-    const float gc = dv.g_t[e];
-    dv.g_c[e] = gc;
-    d = (float)(st.cg * (double)gc);
-    dv.d[e] = d;
-  } else if (st.action == kActAccept || st.action == kActAcceptDone) {
-    x = (float)((double)x + st.t_acc * (double)d);
-    dv.x[e] = x;
-    if (st.action == kActAccept) {
-      const float gt = dv.g_t[e], gc = dv.g_c[e];
-      if (st.push_slot >= 0) {
-        dv.S[(size_t)st.push_slot * dv.nv + e] = (float)(st.t_acc * (double)d);
-        dv.Y[(size_t)st.push_slot * dv.nv + e] = gt - gc;
-      }
-      dv.g_c[e] = gt;
-      double nd = st.cg * (double)gt;
-      for (int i = 0; i < dv.H; ++i)  // (this thread alone wrote element e of the pushed pair)
-        nd += st.cs[i] * (double)dv.S[(size_t)i * dv.nv + e] + st.cy[i] * (double)dv.Y[(size_t)i * dv.nv + e];
-      d = (float)nd;
-      dv.d[e] = d;
-    }
-  }
-  if (st.action == kActInit || st.action == kActTrial || st.action == kActAccept)
-    fit_write_trial(dv, e, (float)((double)x + st.t * (double)d));
+  fit_update_body(dv, st, e, [&](int i, float bt) { fit_write_trial(dv, i, bt); });
 }
 
 // Back to the original feature space: coef = beta / sigma, coefficients centred over

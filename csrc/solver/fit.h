@@ -7,6 +7,7 @@
 // solver's controller (ctrl_step of solver_ctrl.h: the same line search and compact
 // L-BFGS, with no slot budget) and launches fit_update with the resulting action,
 // whose scalars travel as kernel arguments.  No ring, no slot limit, no graph.
+// The loop itself is FitLoop (fit_loop.h), shared with the wide fitter.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -15,16 +16,9 @@
 #include <vector>
 
 #include "../kernels/fit_kernels.h"
+#include "fit_loop.h"
 
 namespace psx {
-
-struct FitOpts {
-  int max_iter = 100;
-  double tol = 1e-6;
-  double reg_param = 0.0;
-  int ls_max = 20;
-  int zero_const = 1;
-};
 
 class BatchFitter {
  public:
@@ -48,15 +42,15 @@ class BatchFitter {
   void current(float* w_out, hipStream_t s);
   void read_std(float* std_out, hipStream_t s);
 
-  bool done() const { return done_; }
-  const std::string& reason() const { return reason_; }
-  int evals() const { return ctrl_.evals; }
-  int accepted() const { return ctrl_.nacc; }
-  int ls_fail() const { return ctrl_.ls_fail; }
-  int dir_reset() const { return ctrl_.dir_reset; }
-  double objective() const { return ctrl_.f_c; }
-  double log_loss() const { return log_loss_; }
-  const std::vector<double>& history() const { return history_; }
+  bool done() const { return loop_.done(); }
+  const std::string& reason() const { return loop_.reason(); }
+  int evals() const { return loop_.ctrl().evals; }
+  int accepted() const { return loop_.ctrl().nacc; }
+  int ls_fail() const { return loop_.ctrl().ls_fail; }
+  int dir_reset() const { return loop_.ctrl().dir_reset; }
+  double objective() const { return loop_.ctrl().f_c; }
+  double log_loss() const { return loop_.log_loss(); }
+  const std::vector<double>& history() const { return loop_.history(); }
   const std::vector<double>& eval_seconds() const { return eval_s_; }
   int grid() const { return G_; }
 
@@ -67,16 +61,8 @@ class BatchFitter {
   void* ws_ = nullptr;
   void* data_ws_ = nullptr;  // per-dataset partials (sized by the grid)
   double* pin_ = nullptr;
-  FitOpts opts_{};
-  SolverCfg cfg_{};
-  Ctrl ctrl_{};
-  CtrlScratch scratch_{};
-  bool begun_ = false, done_ = true;
-  int slot_ = 0;
-  long long max_evals_ = 0;
-  double log_loss_ = 0.0;
-  std::string reason_;
-  std::vector<double> history_, eval_s_;
+  FitLoop loop_;
+  std::vector<double> eval_s_;
 };
 
 }  // namespace psx

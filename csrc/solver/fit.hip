@@ -75,8 +75,7 @@ void BatchFitter::set_data(const uint16_t* X, const int32_t* y, int64_t N, int64
   if (N < 1 || N >= INT_MAX - 64) throw std::invalid_argument("row count must be in [1, 2^31 - 64)");
   if (Npad != (N + 31) / 32 * 32) throw std::invalid_argument("the rows must be padded to a multiple of 32");
   if (!X || !y) throw std::invalid_argument("null rows or labels");
-  begun_ = false;
-  done_ = true;
+  loop_.stop();
   dv_.X = X;
   dv_.y = y;
   dv_.N = (int)N;
@@ -113,8 +112,7 @@ void BatchFitter::evaluate(double reg, int raw, hipStream_t s) {
 double BatchFitter::loss_grad(const float* w, float* grad, hipStream_t s) {
   if (!dv_.X) throw std::runtime_error("loss_grad: no dataset (set_data first)");
   if (!w || !grad) throw std::invalid_argument("loss_grad: null weights or gradient buffer");
-  begun_ = false;  // the trial fragments are overwritten
-  done_ = true;
+  loop_.stop();  // the trial fragments are overwritten
   launch_fit_begin(dv_, w, 1, /*raw=*/1, s);
   evaluate(0.0, /*raw=*/1, s);
   eval_s_.pop_back();
@@ -126,91 +124,25 @@ double BatchFitter::loss_grad(const float* w, float* grad, hipStream_t s) {
 void BatchFitter::begin(const float* w0, const FitOpts& o, hipStream_t s) {
   if (!dv_.X) throw std::runtime_error("fit: no dataset (set_data first)");
   if (dv_.N < 2) throw std::invalid_argument("fit: at least 2 rows are needed");
-  if (o.reg_param < 0.0 || !(o.reg_param == o.reg_param)) throw std::invalid_argument("fit: reg_param must be >= 0");
-  if (o.max_iter < 0 || o.ls_max < 1 || o.tol < 0.0) throw std::invalid_argument("fit: bad max_iter / ls_max / tol");
-  opts_ = o;
-  cfg_ = SolverCfg{};
-  cfg_.K = dv_.K;
-  cfg_.F = dv_.F;
-  cfg_.Fp = dv_.FP;
-  cfg_.P = dv_.n;
-  cfg_.cap = dv_.Npad;
-  cfg_.iters = o.max_iter;
-  cfg_.hist = dv_.H;
-  cfg_.ls_max = o.ls_max;
-  cfg_.mode = kModeLBFGS;
-  cfg_.center = o.reg_param == 0.0;
-  cfg_.zero_const = o.zero_const;
-  cfg_.nslots = INT_MAX;  // the slot budget never fires
-  cfg_.tol = (float)o.tol;
-  ctrl_init(ctrl_);
-  slot_ = 0;
-  max_evals_ = (long long)o.max_iter * o.ls_max + 1;
-  history_.clear();
+  loop_.start(o, dv_.H);
   eval_s_.clear();
-  reason_.clear();
-  log_loss_ = 0.0;
   launch_fit_begin(dv_, w0, o.zero_const, /*raw=*/0, s);
   hip_check(hipGetLastError(), "fit_begin launch");
-  begun_ = true;
-  done_ = false;
 }
 
 bool BatchFitter::run(int max_accept, hipStream_t s) {
-  if (!begun_) throw std::runtime_error("fit: begin() first");
-  const int nacc0 = ctrl_.nacc;
-  while (!done_) {
-    if (ctrl_.evals >= max_evals_) {  // never expected: every line search ends within ls_max evaluations
-      reason_ = "max_iter";
-      done_ = true;
-      break;
-    }
-    evaluate(opts_.reg_param, 0, s);
-    const double f_t = pin_[kFitOutF];
-    const int phase0 = ctrl_.phase, nacc_prev = ctrl_.nacc;
-    ctrl_step(ctrl_, cfg_, f_t, pin_ + kFitOutDots, slot_, scratch_);
-    if (slot_ < INT_MAX - 2) ++slot_;
-    if (phase0 == kPhInit) {
-      history_.push_back(f_t);
-      log_loss_ = pin_[kFitOutLoss];
-    } else if (ctrl_.nacc > nacc_prev) {
-      history_.push_back(ctrl_.f_c);
-      log_loss_ = pin_[kFitOutLoss];
-    }
-    if (ctrl_.action != kActDone && ctrl_.action != kActNone) {
-      FitStep st{};
-      st.action = ctrl_.action;
-      st.push_slot = ctrl_.push_slot;
-      st.t = ctrl_.t;
-      st.t_acc = ctrl_.t_acc;
-      st.cg = ctrl_.cg;
-      for (int i = 0; i < kMaxHist; ++i) {
-        st.cs[i] = ctrl_.cs[i];
-        st.cy[i] = ctrl_.cy[i];
-      }
-      launch_fit_update(dv_, st, s);
-      hip_check(hipGetLastError(), "fit_update launch");
-    }
-    if (ctrl_.phase == kPhDone) {
-      done_ = true;
-      const bool finite = std::isfinite(f_t);
-      if (ctrl_.action == kActAcceptDone)
-        reason_ = ctrl_.iter >= cfg_.iters ? "max_iter" : "tol";
-      else if (phase0 == kPhInit)  // ended at the starting point
-        reason_ = !finite ? "no_descent" : (cfg_.iters <= 0 ? "max_iter" : "tol");
-      else  // a line search spent its budget without sufficient decrease (or met a non-finite objective)
-        reason_ = finite ? "line_search" : "no_descent";
-      break;
-    }
-    if (ctrl_.nacc - nacc0 >= max_accept) break;
-  }
-  return done_;
+  return loop_.run(
+      max_accept, pin_, [&](double reg) { evaluate(reg, 0, s); },
+      [&](const FitStep& st) {
+        launch_fit_update(dv_, st, s);
+        hip_check(hipGetLastError(), "fit_update launch");
+      });
 }
 
 void BatchFitter::current(float* w_out, hipStream_t s) {
-  if (!begun_) throw std::runtime_error("fit: begin() first");
+  if (!loop_.begun()) throw std::runtime_error("fit: begin() first");
   if (!w_out) throw std::invalid_argument("fit: null output buffer");
-  launch_fit_finalize(dv_, opts_.reg_param == 0.0, w_out, s);
+  launch_fit_finalize(dv_, loop_.opts().reg_param == 0.0, w_out, s);
   hip_check(hipGetLastError(), "fit_finalize launch");
   hip_check(hipStreamSynchronize(s), "hipStreamSynchronize(fit_finalize)");
 }

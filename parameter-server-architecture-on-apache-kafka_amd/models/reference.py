@@ -308,6 +308,8 @@ def fit_reference(
     hist: int = 10,
     ls_max: int = 20,
     zero_const: bool = True,
+    loss_grad=None,
+    std: torch.Tensor | None = None,
 ) -> FitReference:
     """Fit to convergence: Spark's ``LogisticRegression.fit`` with
     ``standardization=true``, ``elasticNetParam=0``.
@@ -318,9 +320,19 @@ def fit_reference(
     same L-BFGS, strong-Wolfe line search and stopping tests, float64 -- without the
     slot budget, with the L2 term, a per-iteration objective history and a
     termination reason.  Intercepts are always centred over the classes, coefficients
-    only when ``reg_param == 0`` (with a penalty the optimum is centred by itself)."""
-    X = X.double()
+    only when ``reg_param == 0`` (with a penalty the optimum is centred by itself); a
+    one-logit fit (K == 1, the sigmoid model) is not centred at all.
+
+    ``loss_grad(coef_eff, b) -> (loss, d/dcoef, d/db)`` replaces
+    ``multinomial_loss_grad(X, y, ., .)`` and ``std`` replaces ``feature_std(X)``: the
+    wide fit passes float64 sparse closures over the touched columns (``X`` may then
+    be ``None``, with ``coef0`` given)."""
+    if X is not None:
+        X = X.double()
     y = y.long()
+    if loss_grad is None:
+        def loss_grad(ce, bb):
+            return multinomial_loss_grad(X, y, ce, bb)
     if coef0 is None:
         if num_classes is None:
             raise ValueError("fit_reference needs num_classes or a start")
@@ -329,7 +341,7 @@ def fit_reference(
     w_old = coef0.double()
     b_old = torch.zeros(K, dtype=torch.float64) if intercept0 is None else intercept0.double()
     lam = float(reg_param)
-    sd = feature_std(X)
+    sd = feature_std(X) if std is None else std.double()
     live = sd > 0
     inv = torch.where(live, 1.0 / torch.where(live, sd, torch.ones_like(sd)), torch.zeros_like(sd))
     wfix = torch.zeros_like(w_old) if zero_const else torch.where(live, torch.zeros_like(w_old), w_old)
@@ -337,7 +349,7 @@ def fit_reference(
 
     def fg(v):
         c, b = v[: K * F].view(K, F), v[K * F :]
-        loss, gc, gb = multinomial_loss_grad(X, y, c * inv + wfix, b)
+        loss, gc, gb = loss_grad(c * inv + wfix, b)
         f, g = float(loss), torch.cat([(gc * inv).reshape(-1), gb])
         last["loss"] = f
         if lam != 0.0:
@@ -455,8 +467,9 @@ def fit_reference(
         t = 1.0
     c, b = x[: K * F].view(K, F), x[K * F :]
     coef = torch.where(live, c * inv, wfix)
-    if lam == 0.0:
+    if lam == 0.0 and K > 1:
         coef = coef - coef.mean(0, keepdim=True)
-    b = b - b.mean()
+    if K > 1:
+        b = b - b.mean()
     return FitReference(coef=coef, intercept=b, std=sd, objective=f_c, log_loss=log_loss, history=history, iters=it,
                         evals=evals, ls_fail=ls_fail, reason=reason)

@@ -36,6 +36,7 @@ import torch
 from .. import _native
 from ..models.logreg import ModelSpec, to_reference_layout
 from ..models.reference import fit_reference
+from ..models.wide import WideSpec
 from ..utils.checkpoint import CKPT_NAME, FORMAT, _atomic_save
 from ..utils.data import Dataset
 from .lr import is_gpu, stream_handle
@@ -69,6 +70,9 @@ class FitResult:
     valid_history: list = field(default_factory=list)  # (accepted iterations, validation log-loss)
     best_iter: int | None = None  # the iterate ``w`` holds when a validation set chose it
     ls_fail: int = 0  # line searches that spent their budget (settled for sufficient decrease, or ended the fit)
+    # a wide fit (psx/ops/wide_fit.py): ``spec`` is a WideSpec, ``features`` int32 [U] the sorted features the
+    # training set touches and ``std`` their [U] sigmas (every other feature is excluded: sigma 0, coefficient 0)
+    features: torch.Tensor | None = None
 
     def save(self, path_dir: str) -> str:
         """Write ``server.ckpt`` into ``path_dir`` (for ``Scorer.from_checkpoint`` /
@@ -80,8 +84,11 @@ class FitResult:
                    evals=int(self.evals), ls_fail=int(self.ls_fail), reason=str(self.reason),
                    seconds=float(self.seconds), history=[float(v) for v in self.history])
         state = {"format": FORMAT, "model": "dense", "num_features": int(self.spec.F),
-                 "num_classes": int(self.spec.K), "w": w, "w_reference_layout": to_reference_layout(self.spec, w),
-                 "fit": fit}
+                 "num_classes": int(self.spec.K), "w": w, "fit": fit}
+        if isinstance(self.spec, WideSpec):  # the wide layout is the reference's own flat order: no second copy
+            state["model"] = "wide"
+        else:
+            state["w_reference_layout"] = to_reference_layout(self.spec, w)
         return _atomic_save(state, os.path.join(path_dir, CKPT_NAME))
 
 
@@ -117,6 +124,49 @@ def _check_data(spec: ModelSpec, ds, min_rows: int):
     lo, hi = int(ds.y.min()), int(ds.y.max())
     if lo < 0 or hi >= spec.K:
         raise ValueError(f"labels span [{lo}, {hi}], the model has classes [0, {spec.K})")
+
+
+def _run_native(nat, st, w, check, valid_every, patience):
+    """Drive a native fitter (begun) to its end, finalising the iterate into ``w``;
+    with ``check`` the iterate is scored every ``valid_every`` accepted iterations.
+    -> (best, validation history, ``early_stop`` or None); best = (validation
+    log-loss, accepted iterations, weights, objective, log-loss) or None."""
+    best, vhist, bad = None, [], 0
+    while True:
+        ended = nat.run(valid_every if check else (1 << 30), st)
+        nat.current(w.data_ptr(), st)
+        if check:
+            v = check(w)
+            vhist.append((int(nat.accepted), v))
+            if best is None or v < best[0]:
+                best, bad = (v, int(nat.accepted), w.clone(), float(nat.objective), float(nat.log_loss)), 0
+            else:
+                bad += 1
+                if patience is not None and bad >= patience and not ended:
+                    return best, vhist, "early_stop"
+        if ended:
+            return best, vhist, None
+
+
+def _validate_oracle(res, ref, run, pack, check, valid_every, patience):
+    """Validation of a CPU fit.  The oracle is deterministic: its iterate after i
+    accepted iterations is the fit capped at i (``run(i)``)."""
+    best, bad = None, 0
+    marks = list(range(valid_every, ref.iters, valid_every)) + [ref.iters]
+    for i in marks:
+        r = ref if i == ref.iters else run(i)
+        w = pack(r)
+        v = check(w)
+        res.valid_history.append((i, v))
+        if best is None or v < best[0]:
+            best, bad = (v, i, w, r.objective, r.log_loss), 0
+        else:
+            bad += 1
+            if patience is not None and bad >= patience and i != ref.iters:
+                res.reason = "early_stop"
+                res.iters, res.history = i, list(ref.history[: i + 1])
+                break
+    res.w, res.best_iter, res.objective, res.log_loss = best[2], best[1], best[3], best[4]
 
 
 class _Resident:
@@ -235,24 +285,8 @@ class BatchFitter:
         nat.begin(w0d.data_ptr() if w0d is not None else 0, int(o.max_iter), float(o.tol), float(o.reg_param),
                   int(o.ls_max), bool(o.zero_const), st)
         w = torch.empty(s.P, dtype=torch.float32, device=dev)
-        best = None  # (validation log-loss, accepted iterations, weights, objective, log-loss)
-        vhist, bad, reason = [], 0, None
         check = self._validator(valid) if valid is not None else None
-        while True:
-            ended = nat.run(valid_every if check else (1 << 30), st)
-            nat.current(w.data_ptr(), st)
-            if check:
-                v = check(w)
-                vhist.append((int(nat.accepted), v))
-                if best is None or v < best[0]:
-                    best, bad = (v, int(nat.accepted), w.clone(), float(nat.objective), float(nat.log_loss)), 0
-                else:
-                    bad += 1
-                    if patience is not None and bad >= patience and not ended:
-                        reason = "early_stop"
-                        break
-            if ended:
-                break
+        best, vhist, reason = _run_native(nat, st, w, check, valid_every, patience)
         std = torch.empty(s.Fp, dtype=torch.float32, device=dev)
         nat.read_std(std.data_ptr(), st)
         ev = list(nat.eval_seconds)
@@ -285,26 +319,9 @@ class BatchFitter:
                         log_loss=ref.log_loss, history=list(ref.history), iters=ref.iters, evals=ref.evals,
                         reason=ref.reason, std=ref.std.float(), seconds=0.0, pass_seconds=dt / max(1, ref.evals),
                         options=o, ls_fail=ref.ls_fail)
-        if valid is None:
-            return res
-        # the oracle is deterministic: its iterate after i accepted iterations is the fit capped at i
-        check = self._validator(valid)
-        best, bad = None, 0
-        marks = list(range(valid_every, ref.iters, valid_every)) + [ref.iters]
-        for i in marks:
-            r = ref if i == ref.iters else run(i)
-            w = s.pack(r.coef, r.intercept, device=self.device)
-            v = check(w)
-            res.valid_history.append((i, v))
-            if best is None or v < best[0]:
-                best, bad = (v, i, w, r.objective, r.log_loss), 0
-            else:
-                bad += 1
-                if patience is not None and bad >= patience and i != ref.iters:
-                    res.reason = "early_stop"
-                    res.iters, res.history = i, list(ref.history[: i + 1])
-                    break
-        res.w, res.best_iter, res.objective, res.log_loss = best[2], best[1], best[3], best[4]
+        if valid is not None:
+            _validate_oracle(res, ref, run, lambda r: s.pack(r.coef, r.intercept, device=self.device),
+                             self._validator(valid), valid_every, patience)
         return res
 
 
