@@ -831,8 +831,11 @@ __device__ __forceinline__ void bwd_body(const SolverCfg& cfg, const SolveParams
     if (i >= H) i -= H;
     si = 0.0;
     yi = 0.0;
+    // (own: the persistent forms keep the pairs in LDS and write only the KP owned classes;
+    // the other threads' words are whatever the LDS held -- 0 * Inf would poison the dot)
 #pragma unroll
     for (int e = 0; e < NE; ++e) {
+      if (!own[e]) continue;
       si += (double)s_at(i, e) * g[e];
       yi += (double)y_at(i, e) * g[e];
     }
@@ -1051,7 +1054,8 @@ __device__ __forceinline__ void bwd_body(const SolverCfg& cfg, const SolveParams
         continue;
       }
 #pragma unroll
-      for (int e = 0; e < NE; ++e) dn[e] += cs * s_at(i, e) + cy * y_at(i, e);
+      for (int e = 0; e < NE; ++e)
+        if (own[e]) dn[e] += cs * s_at(i, e) + cy * y_at(i, e);
       if (ib) dbv += cs * sb_at(i) + cy * yb_at(i);
     }
 #pragma unroll
