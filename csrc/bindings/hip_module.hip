@@ -305,20 +305,28 @@ PYBIND11_MODULE(_psx_hip, m) {
   m.def(
       "score",
       [](int FP, int K, uintptr_t X, uintptr_t y, int T, uintptr_t whi, uintptr_t wlo, uintptr_t b, uintptr_t pred,
-         uintptr_t proba, uintptr_t nll, uintptr_t conf, uintptr_t oor, uintptr_t stream) {
+         uintptr_t proba, uintptr_t nll, uintptr_t conf, uintptr_t oor, uintptr_t stream, uintptr_t hist,
+         int hist_form) {
         if (!fp_supported(FP) || K < 2 || K > 16) throw std::invalid_argument("score: unsupported FP or K");
         if (!pred) throw std::invalid_argument("score: null prediction buffer");
         if (y && (!conf || !oor)) throw std::invalid_argument("score: labels need the count buffers");
         if (nll && !y) throw std::invalid_argument("score: the per-row loss needs labels");
+        if (hist && !y) throw std::invalid_argument("score: the score histogram needs labels");
+        if (hist_form != 0 && hist_form != kHistLds && hist_form != kHistGlobal)
+          throw std::invalid_argument("score: hist_form is 0 (auto), 1 (LDS table) or 2 (global atomics)");
         prepare_score_kernels();
-        const ScoreOut o{P<int32_t>(pred), P<float>(proba), P<float>(nll), P<int>(conf), P<int>(oor)};
-        launch_score(FP, K, P<const uint16_t>(X), P<const int32_t>(y), T, P<const uint16_t>(whi),
-                     P<const uint16_t>(wlo), P<const float>(b), o, S(stream));
+        const ScoreOut o{P<int32_t>(pred), P<float>(proba), P<float>(nll), P<int>(conf), P<int>(oor), P<int>(hist)};
+        if (!launch_score(FP, K, P<const uint16_t>(X), P<const int32_t>(y), T, P<const uint16_t>(whi),
+                          P<const uint16_t>(wlo), P<const float>(b), o, S(stream), hist_form))
+          throw std::invalid_argument("score: the LDS histogram table of " + std::to_string(K) +
+                                      " classes does not fit beside an FP " + std::to_string(FP) + " tile");
         hip_check(hipGetLastError(), "score launch");
       },
       py::arg("FP"), py::arg("K"), py::arg("X"), py::arg("y"), py::arg("T"), py::arg("whi"), py::arg("wlo"),
       py::arg("b"), py::arg("pred"), py::arg("proba") = 0, py::arg("nll") = 0, py::arg("conf") = 0,
-      py::arg("oor") = 0, py::arg("stream") = 0);
+      py::arg("oor") = 0, py::arg("stream") = 0, py::arg("hist") = 0, py::arg("hist_form") = 0);
+  // The form launch_score picks for the histogram by itself: 1 = LDS table, 2 = global atomics.
+  m.def("score_hist_form", &score_hist_form, py::arg("FP"), py::arg("K"));
   // Full-batch trainer (psx/ops/fit.py): the host loop of a fit runs with the GIL released.
   py::class_<BatchFitter>(m, "BatchFitter")
       .def(py::init<int, int, int, int, int>(), py::arg("K"), py::arg("F"), py::arg("FP"), py::arg("hist") = 10,
@@ -753,20 +761,23 @@ PYBIND11_MODULE(_psx_hip, m) {
   m.def(
       "wide_score",
       [](int K, int KP, int64_t F, uintptr_t indptr, uintptr_t idx, uintptr_t val, uintptr_t y, int T, uintptr_t w,
-         uintptr_t pred, uintptr_t proba, uintptr_t nll, uintptr_t conf, uintptr_t oor, uintptr_t stream) {
+         uintptr_t pred, uintptr_t proba, uintptr_t nll, uintptr_t conf, uintptr_t oor, uintptr_t stream,
+         uintptr_t hist) {
         if (K < 1 || K > KP || (KP != 1 && KP != 2 && KP != 4 && KP != 8 && KP != 16))
           throw std::invalid_argument("wide_score: unsupported K / KP");
         if (!pred) throw std::invalid_argument("wide_score: null prediction buffer");
         if (y && (!conf || !oor)) throw std::invalid_argument("wide_score: labels need the count buffers");
         if (nll && !y) throw std::invalid_argument("wide_score: the per-row loss needs labels");
-        const ScoreOut o{P<int32_t>(pred), P<float>(proba), P<float>(nll), P<int>(conf), P<int>(oor)};
+        if (hist && !y) throw std::invalid_argument("wide_score: the score histogram needs labels");
+        if (hist) prepare_score_kernels();  // the table's dynamic-LDS limit
+        const ScoreOut o{P<int32_t>(pred), P<float>(proba), P<float>(nll), P<int>(conf), P<int>(oor), P<int>(hist)};
         launch_wide_score(K, KP, F, P<const int64_t>(indptr), P<const int32_t>(idx), P<const uint16_t>(val),
                           P<const int32_t>(y), T, P<const float>(w), o, S(stream));
         hip_check(hipGetLastError(), "wide_score launch");
       },
       py::arg("K"), py::arg("KP"), py::arg("F"), py::arg("indptr"), py::arg("idx"), py::arg("val"), py::arg("y"),
       py::arg("T"), py::arg("w"), py::arg("pred"), py::arg("proba") = 0, py::arg("nll") = 0, py::arg("conf") = 0,
-      py::arg("oor") = 0, py::arg("stream") = 0);
+      py::arg("oor") = 0, py::arg("stream") = 0, py::arg("hist") = 0);
   m.def("wide_apply_sparse", [](uintptr_t w, int64_t F, int KP, uintptr_t U_dev, int U_host, uintptr_t uniq,
                                 uintptr_t dloc, float lr, int umax, uintptr_t stream) {
     launch_wide_apply_sparse(P<float>(w), F, KP, P<const unsigned>(U_dev), U_host, P<const int32_t>(uniq),

@@ -38,6 +38,21 @@ __device__ __forceinline__ void flush_counts(const int* cl, const int* noor, con
   if (threadIdx.x == 0 && *noor) atomicAdd(o.oor, *noor);
 }
 
+// Score-histogram bin of a one-vs-rest log-odds l (score_kernels.h): clamped in
+// float before the conversion, so +inf lands in bin 511, -inf and NaN in bin 0
+// (fmaxf returns its other operand for a NaN).
+__device__ __forceinline__ int hist_bin(float l) {
+  return 256 + (int)fminf(fmaxf(rintf(16.f * l), -256.f), 255.f);
+}
+
+// workgroup table [Ch][2][512] -> one global integer atomic per non-zero cell
+__device__ __forceinline__ void flush_hist(const int* ht, int Ch, int* hist) {
+  for (int i = threadIdx.x; i < Ch * kHistCells; i += 256) {
+    const int v = ht[i];
+    if (v) atomicAdd(hist + i, v);
+  }
+}
+
 }  // namespace
 
 // ---------------------------------------------------------------------------
@@ -47,7 +62,22 @@ __device__ __forceinline__ void flush_counts(const int* cl, const int* noor, con
 // per row on 32 threads and leaves the row's max and sum in LDS; the
 // probabilities -- the only sizeable output stream -- are then written by all
 // 256 threads as one contiguous run of nrows * K floats per tile.
-template <int FP>
+//
+// HM (the score histogram, score_kernels.h): kHistOff is the kernel as it was.
+// Otherwise the epilogue also leaves the row's margins (intercepts included) and
+// its label in LDS, and all 256 threads walk the tile's nrows * K entries as the
+// probability writer does: the log-odds from a direct sum over the other classes,
+// the bin, one integer atomic.  kHistLds counts in a workgroup-private table of
+// K * 4 KB behind eval_lds_bytes(FP), flushed once after the tile loop.  At
+// FP 2048 only 20,992 B are left beside the tile, a table of 5 classes; kHistGlobal
+// is the form for K > 5 there: the same entries, added straight to the global
+// table.  Half-width counters would still need 32 KB at K = 16 and a table
+// resident for part of the classes would walk the entries several times, while
+// global integer atomics need no LDS at all and give the identical table.  They
+// are slow where many rows share a bin (every workgroup adds to the same words:
+// profiles/r14, tools/bench_score.py --curves), so launch_score takes this form
+// only where the LDS table does not fit.
+template <int FP, int HM = kHistOff>
 __global__ __launch_bounds__(256) void score_kernel(int K, const uint16_t* __restrict__ X,
                                                     const int32_t* __restrict__ y, int T,
                                                     const uint16_t* __restrict__ wf_hi,
@@ -59,10 +89,15 @@ __global__ __launch_bounds__(256) void score_kernel(int K, const uint16_t* __res
   float* rmax = (float*)(cl + 256);   // [32] row maximum
   float* rsum = rmax + 32;            // [32] sum of exp(z - max)
   int* noor = (int*)(rsum + 32);
+  int* rlab = noor + 1;                  // [32] the rows' labels            (HM only)
+  float* zt = (float*)(rlab + 32);       // [32][16] margins with intercepts (HM only)
+  int* ht = (int*)(lds + eval_lds_bytes(FP));  // [K][2][512]                (kHistLds only)
   const int tid = threadIdx.x;
   const bool need_sum = o.proba != nullptr || (y != nullptr && o.nll != nullptr);
   cl[tid] = 0;
   if (tid == 0) *noor = 0;
+  if constexpr (HM == kHistLds)
+    for (int i = tid; i < K * kHistCells; i += 256) ht[i] = 0;
   constexpr bool kPre = FP <= 1024;
   WFrag<kPre ? FP : 128> wf;
   if constexpr (kPre) load_wfrag<FP>(wf, wf_hi, wf_lo, K);
@@ -85,11 +120,13 @@ __global__ __launch_bounds__(256) void score_kernel(int K, const uint16_t* __res
       float bz = -INFINITY;
       for (int c = 0; c < K; ++c) {
         const float z = load_logit(red_base, tid, c) + b[c];
+        if constexpr (HM != kHistOff) zt[tid * 16 + c] = z;
         if (z > bz) {
           bz = z;
           best = c;
         }
       }
+      if constexpr (HM != kHistOff) rlab[tid] = ylab;
       float s = 0.f;
       if (need_sum)
         for (int c = 0; c < K; ++c) s += expf(load_logit(red_base, tid, c) + b[c] - bz);
@@ -113,9 +150,28 @@ __global__ __launch_bounds__(256) void score_kernel(int K, const uint16_t* __res
         dst[e] = expf(load_logit(red_base, r, c) + b[c] - rmax[r]) / rsum[r];
       }
     }
+    if constexpr (HM != kHistOff) {
+      if (o.proba == nullptr) __syncthreads();  // zt, rlab, rmax (the probability writer has synchronised)
+      for (int e = tid; e < nrows * K; e += 256) {
+        const int r = e / K, c = e - r * K;
+        const int yl = rlab[r];
+        if (yl < 0 || yl >= K) continue;  // counted in oor, enters no cell
+        const float* zr = zt + r * 16;
+        const float m = rmax[r];
+        float so = 0.f;  // over the other classes, never s - e_c
+        for (int j = 0; j < K; ++j)
+          if (j != c) so += expf(zr[j] - m);
+        const int cell = (c * 2 + (yl == c ? 1 : 0)) * kHistBins + hist_bin((zr[c] - m) - logf(so));
+        if constexpr (HM == kHistLds)
+          atomicAdd(ht + cell, 1);
+        else
+          atomicAdd(o.hist + cell, 1);
+      }
+    }
     __syncthreads();
   }
   if (y != nullptr) flush_counts(cl, noor, o);
+  if constexpr (HM == kHistLds) flush_hist(ht, K, o.hist);
 }
 
 // ---------------------------------------------------------------------------
@@ -123,7 +179,11 @@ __global__ __launch_bounds__(256) void score_kernel(int K, const uint16_t* __res
 // the wave reduction every lane holds the row's margins, so the epilogue needs no
 // further exchange: lane 0 writes the row's scalars, lanes [0, C) its probabilities
 // (the 4 rows of a workgroup pass are adjacent, their C floats contiguous).
-template <int KP>
+//
+// HIST (the score histogram): lane c < Ch also computes the log-odds of class c
+// with a predicated sum over the other classes (binary: the margin itself) and
+// counts it in a workgroup-private LDS table [Ch][2][512], flushed at the end.
+template <int KP, bool HIST = false>
 __global__ __launch_bounds__(256) void wide_score_kernel(int K, int64_t F, const int64_t* __restrict__ indptr,
                                                          const int32_t* __restrict__ idx,
                                                          const uint16_t* __restrict__ val,
@@ -131,11 +191,14 @@ __global__ __launch_bounds__(256) void wide_score_kernel(int K, int64_t F, const
                                                          const float* __restrict__ w, ScoreOut o) {
   __shared__ int cl[256];
   __shared__ int noor;
+  extern __shared__ __attribute__((aligned(16))) int wide_ht[];  // [K][2][512] (HIST only)
   const int tid = threadIdx.x, lane = tid & 63;
   const bool binary = K == 1;
   const int C = binary ? 2 : K;
   cl[tid] = 0;
   if (tid == 0) noor = 0;
+  if constexpr (HIST)
+    for (int i = tid; i < K * kHistCells; i += 256) wide_ht[i] = 0;
   __syncthreads();
   for (int64_t r = (int64_t)blockIdx.x * 4 + (tid >> 6); r < T; r += (int64_t)gridDim.x * 4) {
     float z[KP];
@@ -156,6 +219,20 @@ __global__ __launch_bounds__(256) void wide_score_kernel(int K, int64_t F, const
       for (int k = 0; k < KP; ++k)
         if (k == lane) zl = z[k];
       o.proba[r * C + lane] = binary ? sigmoid_side(z[0], lane) : expf(zl - m) / s;
+    }
+    if constexpr (HIST) {
+      if (lane < K) {
+        const int yl = y[r];
+        float zl = 0.f, so = 0.f;
+#pragma unroll
+        for (int k = 0; k < KP; ++k) {
+          if (k == lane) zl = z[k];
+          if (k < K && k != lane) so += expf(z[k] - m);
+        }
+        const float l = binary ? z[0] : (zl - m) - logf(so);
+        const int side = binary ? (yl > 0 ? 1 : 0) : (yl == lane ? 1 : 0);
+        if (binary || (yl >= 0 && yl < K)) atomicAdd(&wide_ht[(lane * 2 + side) * kHistBins + hist_bin(l)], 1);
+      }
     }
     if (lane == 0) {
       o.pred[r] = best;
@@ -182,6 +259,7 @@ __global__ __launch_bounds__(256) void wide_score_kernel(int K, int64_t F, const
   }
   __syncthreads();
   if (y != nullptr) flush_counts(cl, &noor, o);
+  if constexpr (HIST) flush_hist(wide_ht, K, o.hist);
 }
 
 // ---------------------------------------------------------------------------
@@ -189,6 +267,18 @@ template <int FP>
 static void set_score_lds_attr() {
   (void)hipFuncSetAttribute((const void*)score_kernel<FP>, hipFuncAttributeMaxDynamicSharedMemorySize,
                             (int)eval_lds_bytes(FP));
+  (void)hipFuncSetAttribute((const void*)score_kernel<FP, kHistGlobal>, hipFuncAttributeMaxDynamicSharedMemorySize,
+                            (int)eval_lds_bytes(FP));
+  const size_t room = kLdsPerWorkgroup - eval_lds_bytes(FP);
+  const size_t table = room < 16 * kHistCells * 4 ? room / (kHistCells * 4) * (kHistCells * 4) : 16 * kHistCells * 4;
+  (void)hipFuncSetAttribute((const void*)score_kernel<FP, kHistLds>, hipFuncAttributeMaxDynamicSharedMemorySize,
+                            (int)(eval_lds_bytes(FP) + table));
+}
+
+template <int KP>
+static void set_wide_hist_lds_attr() {  // 64 KB of table at K = 16, beside 1 KB of static LDS
+  (void)hipFuncSetAttribute((const void*)wide_score_kernel<KP, true>, hipFuncAttributeMaxDynamicSharedMemorySize,
+                            KP * kHistCells * 4);
 }
 
 void prepare_score_kernels() {
@@ -199,18 +289,37 @@ void prepare_score_kernels() {
   set_score_lds_attr<512>();
   set_score_lds_attr<1024>();
   set_score_lds_attr<2048>();
+  set_wide_hist_lds_attr<1>();
+  set_wide_hist_lds_attr<2>();
+  set_wide_hist_lds_attr<4>();
+  set_wide_hist_lds_attr<8>();
+  set_wide_hist_lds_attr<16>();
   done = true;
 }
 
-void launch_score(int FP, int K, const uint16_t* X, const int32_t* y, int T, const uint16_t* wf_hi,
-                  const uint16_t* wf_lo, const float* b, const ScoreOut& o, hipStream_t s) {
-  const size_t lds = eval_lds_bytes(FP);
+int score_hist_form(int FP, int K) {
+  return eval_lds_bytes(FP) + (size_t)K * kHistCells * 4 <= kLdsPerWorkgroup ? kHistLds : kHistGlobal;
+}
+
+bool launch_score(int FP, int K, const uint16_t* X, const int32_t* y, int T, const uint16_t* wf_hi,
+                  const uint16_t* wf_lo, const float* b, const ScoreOut& o, hipStream_t s, int hist_form) {
+  int hm = kHistOff;
+  if (o.hist != nullptr && y != nullptr) {
+    hm = hist_form ? hist_form : score_hist_form(FP, K);
+    if (hm == kHistLds && score_hist_form(FP, K) != kHistLds) return false;
+  }
+  const size_t lds = eval_lds_bytes(FP) + (hm == kHistLds ? (size_t)K * kHistCells * 4 : 0);
   const int ntiles = (T + 31) / 32;
   const int grid = ntiles < 1024 ? ntiles : 1024;
-  if (grid <= 0) return;
-#define PSX_SC(FPV)                                                            \
-  case FPV:                                                                    \
-    score_kernel<FPV><<<grid, 256, lds, s>>>(K, X, y, T, wf_hi, wf_lo, b, o); \
+  if (grid <= 0) return true;
+#define PSX_SC(FPV)                                                                             \
+  case FPV:                                                                                     \
+    if (hm == kHistLds)                                                                         \
+      score_kernel<FPV, kHistLds><<<grid, 256, lds, s>>>(K, X, y, T, wf_hi, wf_lo, b, o);    \
+    else if (hm == kHistGlobal)                                                                 \
+      score_kernel<FPV, kHistGlobal><<<grid, 256, lds, s>>>(K, X, y, T, wf_hi, wf_lo, b, o); \
+    else                                                                                        \
+      score_kernel<FPV><<<grid, 256, lds, s>>>(K, X, y, T, wf_hi, wf_lo, b, o);              \
     break;
   switch (FP) {
     PSX_SC(128)
@@ -222,6 +331,7 @@ void launch_score(int FP, int K, const uint16_t* X, const int32_t* y, int T, con
       break;
   }
 #undef PSX_SC
+  return true;
 }
 
 void launch_wide_score(int K, int KP, int64_t F, const int64_t* indptr, const int32_t* idx, const uint16_t* val,
@@ -229,9 +339,13 @@ void launch_wide_score(int K, int KP, int64_t F, const int64_t* indptr, const in
   if (T <= 0) return;
   const int nwg = (T + 3) / 4;  // 4 rows per workgroup pass
   const int grid = nwg < 1024 ? nwg : 1024;
-#define PSX_WS(KV)                                                                    \
-  case KV:                                                                            \
-    wide_score_kernel<KV><<<grid, 256, 0, s>>>(K, F, indptr, idx, val, y, T, w, o); \
+  const bool hist = o.hist != nullptr && y != nullptr;
+#define PSX_WS(KV)                                                                                                  \
+  case KV:                                                                                                          \
+    if (hist)                                                                                                       \
+      wide_score_kernel<KV, true><<<grid, 256, K * kHistCells * 4, s>>>(K, F, indptr, idx, val, y, T, w, o);     \
+    else                                                                                                            \
+      wide_score_kernel<KV><<<grid, 256, 0, s>>>(K, F, indptr, idx, val, y, T, w, o);                            \
     break;
   switch (KP) {
     PSX_WS(1)

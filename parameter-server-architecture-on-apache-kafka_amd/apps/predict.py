@@ -2,12 +2,18 @@
 
 Usage: python -m psx.apps.predict --checkpoint_dir DIR --data test.csv [--out preds.csv] [--proba]
            [--ignore_labels] [--chunk_rows N] [--device ...] [--header auto|yes|no] [--label_col -1]
+           [--curves] [--curves_out FILE.json]
 
 The data file is a CSV or a binary row cache for a dense model, LIBSVM text for a
 wide one.  The loaders always parse a label column; a file without real labels
 carries a placeholder there, and ``--ignore_labels`` leaves the metrics and the
 per-row loss out.  ``--out`` gets one line per row, ``row,pred[,label,nll][,p0..]``;
 stdout gets one JSON line (rows, metrics, the model's shape, rows per second).
+``--curves`` counts the score histogram in the same pass and prints a second JSON
+line after that one: ``auc_macro``, ``auc_weighted``, ``ap_macro``, ``ece`` and the
+per-class one-vs-rest ROC AUC with its resolution; ``--curves_out`` writes the table
+and everything derived from it (it implies ``--curves``).  Curves need labels: with
+``--ignore_labels`` they exit 2.
 ``-h`` exits 0, stray arguments exit 2 (the other front ends' conventions).
 """
 from __future__ import annotations
@@ -35,6 +41,9 @@ def predict_parser():
     ap.add_argument("--device", default=None, help="cpu | cuda | cuda:N (default: cuda if available)")
     ap.add_argument("--header", default="auto", choices=["auto", "yes", "no"])
     ap.add_argument("--label_col", type=int, default=-1)
+    ap.add_argument("--curves", action="store_true",
+                    help="also print ROC AUC, average precision and calibration error (needs labels)")
+    ap.add_argument("--curves_out", default=None, help="write the score histogram and the derived numbers as JSON")
     return ap
 
 
@@ -63,11 +72,35 @@ def write_rows(path: str, res, labels: torch.Tensor | None) -> None:
         np.savetxt(f, np.stack(cols, 1).reshape(res.rows, len(cols)), delimiter=",", fmt=fmts)
 
 
+def _nums(v) -> list:
+    """A float array as JSON: NaN (a class without both sides) becomes null."""
+    return [None if x != x else float(x) for x in np.asarray(v, dtype=np.float64).tolist()]
+
+
+def curves_line(res) -> dict:
+    return {"auc_macro": res.auc_macro, "auc_weighted": res.auc_weighted, "ap_macro": res.ap_macro, "ece": res.ece,
+            "auc": _nums(res.auc), "auc_resolution": _nums(res.auc_resolution)}
+
+
+def write_curves(path: str, res) -> None:
+    from ..utils import metrics as M
+
+    h = res.hist.numpy()
+    doc = curves_line(res)
+    doc.update(ap=_nums(res.ap), ks=_nums(M.ks_statistic(h)), ece_per_class=_nums(M.ece(h)),
+               bins=M.HIST_BINS, bins_per_unit_log_odds=M.HIST_PER_UNIT, hist=res.hist.tolist())
+    with open(path, "w") as f:
+        json.dump(doc, f)
+
+
 def main(argv=None) -> int:
     ap = predict_parser()
     a = parse_or_exit(ap, sys.argv[1:] if argv is None else argv)
     if not a.checkpoint_dir or not a.data:
         ap.error("--checkpoint_dir and --data are required")
+    curves = a.curves or a.curves_out is not None
+    if curves and a.ignore_labels:
+        ap.error("--curves needs labels: it cannot be combined with --ignore_labels")
     from ..ops.score import Scorer
 
     device = a.device or ("cuda:0" if torch.cuda.is_available() else "cpu")
@@ -75,7 +108,7 @@ def main(argv=None) -> int:
     ds = _load(a.data, scorer, a)
     labels = not a.ignore_labels
     t0 = time.perf_counter()
-    res = scorer.score(ds, labels=labels, proba=a.proba, chunk_rows=a.chunk_rows)
+    res = scorer.score(ds, labels=labels, proba=a.proba, chunk_rows=a.chunk_rows, **({"curves": True} if curves else {}))
     if scorer.device.type == "cuda":
         torch.cuda.synchronize(scorer.device)
     dt = time.perf_counter() - t0
@@ -88,6 +121,10 @@ def main(argv=None) -> int:
     line.update(model="wide" if scorer.wide else "dense", num_features=spec.F, num_classes=spec.K,
                 device=str(scorer.device), rows_per_s=res.rows / dt if dt > 0 else 0.0)
     print(json.dumps(line))
+    if curves:
+        print(json.dumps(curves_line(res)))
+        if a.curves_out:
+            write_curves(a.curves_out, res)
     return 0
 
 

@@ -12,7 +12,18 @@ second (rows and labels; the wide model's weight gathers are not counted) and th
 rate as a share of the HBM peak -- the bound that applies: these passes do a few
 FLOPs per byte.
 
-Usage: python tools/bench_score.py [--model dense|wide|both] [--rows N] [--out FILE.json]
+``--curves`` measures the score histogram instead (``score(curves=True)``), with the
+same protocol:
+  * plain      -- ``score`` / ``wide_score`` as above (pred, nll, confusion): the pass
+    the histogram rides in;
+  * proba+hist -- what the tree offered for the same table before: the [T][C]
+    probabilities from the kernel, then torch on the device (log-odds, bins, one
+    ``bincount`` over the class / side / bin cells);
+  * curves     -- the kernel with the histogram (pred, nll, confusion, table);
+and, for the dense model, the same three on 2,048-wide rows with 16 classes (half the
+rows), where the table does not fit in LDS and the kernel adds to the global table.
+
+Usage: python tools/bench_score.py [--model dense|wide|both] [--rows N] [--curves] [--out FILE.json]
 """
 from __future__ import annotations
 
@@ -31,7 +42,7 @@ from psx import _native  # noqa: E402
 from psx.models.logreg import ModelSpec  # noqa: E402
 from psx.models.wide import WideSpec  # noqa: E402
 from psx.ops.lr import stream_handle  # noqa: E402
-from psx.ops.score import Scorer  # noqa: E402
+from psx.ops.score import HIST_FORMS, Scorer  # noqa: E402
 from psx.ops.sparse import SparseDataset  # noqa: E402
 
 HBM_PEAK = 8.0e12  # bytes/s, MI355X HBM3E (datasheet)
@@ -62,7 +73,7 @@ def _report(name: str, ms: dict, nbytes: int) -> dict:
         rate = nbytes / (med * 1e-3)
         out["variants"][k] = {"ms": v, "ms_min": s[0], "ms_median": med, "ms_max": s[-1], "input_bytes_per_s": rate,
                               "share_of_hbm_peak": rate / HBM_PEAK}
-        print(f"{name:6s} {k:9s} ms min/med/max {s[0]:8.3f} {med:8.3f} {s[-1]:8.3f}   {rate / 1e12:6.3f} TB/s input   "
+        print(f"{name:6s} {k:10s} ms min/med/max {s[0]:8.3f} {med:8.3f} {s[-1]:8.3f}   {rate / 1e12:6.3f} TB/s input   "
               f"{100 * rate / HBM_PEAK:5.1f} % of HBM peak (bandwidth bound)")
     return out
 
@@ -74,7 +85,20 @@ def _torch_tail(z, y, K):
     return p, pred, nll
 
 
-def bench_dense(dev, T: int, F: int = 1024, K: int = 6) -> dict:
+def _torch_hist(p, y, K):
+    """The table from [T][C] probabilities: log-odds, the kernels' bins, one bincount."""
+    if K == 1:
+        l = (torch.log(p[:, 1]) - torch.log(p[:, 0])).view(-1, 1)
+        side = (y > 0).long().view(-1, 1)
+    else:
+        l = torch.log(p) - torch.log1p(-p)
+        side = (y.view(-1, 1) == torch.arange(K, device=p.device).view(1, -1)).long()
+    b = 256 + torch.clamp(torch.round(16.0 * l), -256, 255).long()
+    cell = (torch.arange(l.shape[1], device=p.device).view(1, -1) * 2 + side) * 512 + b
+    return torch.bincount(cell.view(-1), minlength=l.shape[1] * 1024)
+
+
+def bench_dense(dev, T: int, F: int = 1024, K: int = 6, curves: bool = False, hist_form: int = 0) -> dict:
     spec = ModelSpec(F, K)
     g = torch.Generator(device=dev).manual_seed(0)
     X = torch.empty(T, spec.Fp, dtype=torch.bfloat16, device=dev)
@@ -83,6 +107,7 @@ def bench_dense(dev, T: int, F: int = 1024, K: int = 6) -> dict:
         X[r0:r1] = (torch.randn(r1 - r0, spec.Fp, generator=g, device=dev) * 0.05).to(torch.bfloat16)
     y = torch.randint(0, K, (T,), generator=g, device=dev).to(torch.int32)
     sc = Scorer(spec, spec.init("random", seed=1, scale=1.0), dev)
+    sc._hist_form = hist_form
     h, st, f = _native.hip(), stream_handle(dev), sc.frag
     z = torch.empty(T, K, dtype=torch.float32, device=dev)
     pred = torch.empty(T, dtype=torch.int32, device=dev)
@@ -94,13 +119,24 @@ def bench_dense(dev, T: int, F: int = 1024, K: int = 6) -> dict:
         h.logits(spec.Fp, K, X.data_ptr(), T, f.hi.data_ptr(), f.lo.data_ptr(), f.b.data_ptr(), z.data_ptr(), st)
         return _torch_tail(z, y, K)
 
+    def proba_hist():
+        sc._dense_gpu(X, y, True, (pred, pr, nll, None), counts)
+        return _torch_hist(pr, y, K)
+
+    if curves:
+        hist = torch.zeros(K * 1024, dtype=torch.int32, device=dev)
+        ms = _time({"plain": lambda: sc._dense_gpu(X, y, True, (pred, None, nll, None), counts),
+                    "proba+hist": proba_hist,
+                    "curves": lambda: sc._dense_gpu(X, y, True, (pred, None, nll, hist), counts)})
+        assert int(hist.sum()) == 4 * T * K  # the warm-up and the three repeats; no sync inside the timing
+        return _report(f"dense F{F} K{K}", ms, T * spec.Fp * 2 + T * 4)
     ms = _time({"baseline": baseline,
-                "fused": lambda: sc._dense_gpu(X, y, True, (pred, None, nll), counts),
-                "fused+p": lambda: sc._dense_gpu(X, y, True, (pred, pr, nll), counts)})
+                "fused": lambda: sc._dense_gpu(X, y, True, (pred, None, nll, None), counts),
+                "fused+p": lambda: sc._dense_gpu(X, y, True, (pred, pr, nll, None), counts)})
     return _report("dense", ms, T * spec.Fp * 2 + T * 4)
 
 
-def bench_wide(dev, T: int, nnz: int = 128, F: int = 1 << 20, K: int = 6) -> dict:
+def bench_wide(dev, T: int, nnz: int = 128, F: int = 1 << 20, K: int = 6, curves: bool = False) -> dict:
     spec = WideSpec(F, K)
     g = torch.Generator(device=dev).manual_seed(0)
     ds = SparseDataset(torch.arange(T + 1, dtype=torch.int64, device=dev) * nnz,
@@ -120,9 +156,20 @@ def bench_wide(dev, T: int, nnz: int = 128, F: int = 1 << 20, K: int = 6) -> dic
                       z.data_ptr(), st)
         return _torch_tail(z[:, :K], ds.y, K)
 
+    def proba_hist():
+        sc._wide_gpu(ds, True, (pred, pr, nll, None), counts)
+        return _torch_hist(pr, ds.y, K)
+
+    if curves:
+        hist = torch.zeros(K * 1024, dtype=torch.int32, device=dev)
+        ms = _time({"plain": lambda: sc._wide_gpu(ds, True, (pred, None, nll, None), counts),
+                    "proba+hist": proba_hist,
+                    "curves": lambda: sc._wide_gpu(ds, True, (pred, None, nll, hist), counts)})
+        assert int(hist.sum()) == 4 * T * K
+        return _report(f"wide K{K}", ms, T * nnz * 6 + (T + 1) * 8 + T * 4)
     ms = _time({"baseline": baseline,
-                "fused": lambda: sc._wide_gpu(ds, True, (pred, None, nll), counts),
-                "fused+p": lambda: sc._wide_gpu(ds, True, (pred, pr, nll), counts)})
+                "fused": lambda: sc._wide_gpu(ds, True, (pred, None, nll, None), counts),
+                "fused+p": lambda: sc._wide_gpu(ds, True, (pred, pr, nll, None), counts)})
     return _report("wide", ms, T * nnz * 6 + (T + 1) * 8 + T * 4)
 
 
@@ -130,6 +177,9 @@ def main(argv=None) -> int:
     ap = argparse.ArgumentParser()
     ap.add_argument("--model", default="both", choices=["dense", "wide", "both"])
     ap.add_argument("--rows", type=int, default=1 << 20)
+    ap.add_argument("--curves", action="store_true", help="measure the score histogram (see the module text)")
+    ap.add_argument("--hist_form", default="auto", choices=sorted(HIST_FORMS),
+                    help="with --curves: the dense kernel's histogram form at the 1,024-wide shape")
     ap.add_argument("--out", default=None, help="also write the results as JSON")
     a = ap.parse_args(argv)
     if not torch.cuda.is_available():
@@ -138,9 +188,13 @@ def main(argv=None) -> int:
     dev = torch.device("cuda:0")
     res = []
     if a.model in ("dense", "both"):
-        res.append(bench_dense(dev, a.rows))
+        res.append(bench_dense(dev, a.rows, curves=a.curves, hist_form=HIST_FORMS[a.hist_form]))
+        if a.curves:
+            torch.cuda.empty_cache()
+            res.append(bench_dense(dev, max(a.rows // 2, 1), F=2048, K=16, curves=True))
+            torch.cuda.empty_cache()
     if a.model in ("wide", "both"):
-        res.append(bench_wide(dev, a.rows))
+        res.append(bench_wide(dev, a.rows, curves=a.curves))
     if a.out:
         with open(a.out, "w") as f:
             json.dump(res, f, indent=1)
