@@ -370,6 +370,17 @@ PYBIND11_MODULE(_psx_hip, m) {
       .def(
           "read_std", [](BatchFitter& f, uintptr_t out, uintptr_t stream) { f.read_std(P<float>(out), S(stream)); },
           py::arg("out"), py::arg("stream") = 0)
+      .def(
+          "read_state",
+          [](BatchFitter& f, uintptr_t x, uintptr_t d, uintptr_t g_c, uintptr_t g_t, uintptr_t beta_t, uintptr_t wfix,
+             uintptr_t Sh, uintptr_t Yh, uintptr_t stream) {
+            f.read_state(P<float>(x), P<float>(d), P<float>(g_c), P<float>(g_t), P<float>(beta_t), P<float>(wfix),
+                         P<float>(Sh), P<float>(Yh), S(stream));
+          },
+          py::arg("x") = 0, py::arg("d") = 0, py::arg("g_c") = 0, py::arg("g_t") = 0, py::arg("beta_t") = 0,
+          py::arg("wfix") = 0, py::arg("S") = 0, py::arg("Y") = 0, py::arg("stream") = 0)
+      .def_property_readonly("n", &BatchFitter::n)
+      .def_property_readonly("nv", &BatchFitter::nv)
       .def_property_readonly("done", &BatchFitter::done)
       .def_property_readonly("reason", &BatchFitter::reason)
       .def_property_readonly("evals", &BatchFitter::evals)
@@ -458,6 +469,17 @@ PYBIND11_MODULE(_psx_hip, m) {
             return f.stage_ms(raw ? 1 : 0, S(stream));
           },
           py::arg("raw"), py::arg("stream") = 0)
+      .def(
+          "read_state",
+          [](WideBatchFitter& f, uintptr_t x, uintptr_t d, uintptr_t g_c, uintptr_t g_t, uintptr_t beta_t, uintptr_t wfix,
+             uintptr_t Sh, uintptr_t Yh, uintptr_t stream) {
+            f.read_state(P<float>(x), P<float>(d), P<float>(g_c), P<float>(g_t), P<float>(beta_t), P<float>(wfix),
+                         P<float>(Sh), P<float>(Yh), S(stream));
+          },
+          py::arg("x") = 0, py::arg("d") = 0, py::arg("g_c") = 0, py::arg("g_t") = 0, py::arg("beta_t") = 0,
+          py::arg("wfix") = 0, py::arg("S") = 0, py::arg("Y") = 0, py::arg("stream") = 0)
+      .def_property_readonly("n", &WideBatchFitter::n)
+      .def_property_readonly("nv", &WideBatchFitter::nv)
       .def_property_readonly("done", &WideBatchFitter::done)
       .def_property_readonly("reason", &WideBatchFitter::reason)
       .def_property_readonly("evals", &WideBatchFitter::evals)
@@ -470,6 +492,7 @@ PYBIND11_MODULE(_psx_hip, m) {
       .def_property_readonly("eval_seconds", &WideBatchFitter::eval_seconds)
       .def_property_readonly("grid", &WideBatchFitter::grid);
   m.attr("wide_fit_short") = kWideFitShort;
+  m.attr("wide_fit_reduce_cap") = kWideReduceMaxWG * 256;  // elements of one trip of the wide reduction
   m.def(
       "server_apply",
       [](int K, int F, int FP, uintptr_t w, uintptr_t delta, float lr, uintptr_t whi, uintptr_t wlo, uintptr_t b,

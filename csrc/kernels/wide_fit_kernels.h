@@ -14,6 +14,7 @@
 namespace psx {
 
 constexpr int kWideFitShort = 32;  // items of up to this many entries take the KP-lane mapping of the column pass
+constexpr int kWideReduceMaxWG = 1024;  // workgroups of the reduction (256 elements each per trip, then grid-stride)
 
 // Device pointers and sizes of one resident dataset (caller-owned, alive until the next
 // set_data): the rows as CSR over the compact columns, the inverted index ordered by

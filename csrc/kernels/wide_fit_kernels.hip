@@ -38,8 +38,6 @@ namespace psx {
 
 namespace {
 
-constexpr int kWideReduceMaxWG = 1024;
-
 template <int KP>
 __device__ __forceinline__ void stk(float* __restrict__ p, const float (&v)[KP]) {
   if constexpr (KP % 4 == 0) {

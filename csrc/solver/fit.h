@@ -41,6 +41,12 @@ class BatchFitter {
   // The current iterate, finalised, -> w_out [K*FP + K] (synchronous).
   void current(float* w_out, hipStream_t s);
   void read_std(float* std_out, hipStream_t s);
+  // Copies of the optimiser's vectors into caller-owned device buffers (nullptr: skip):
+  // x, d, g_c, g_t, beta_t, wfix are [nv], S and Y [hist][nv].  Synchronous, read-only.
+  void read_state(float* x, float* d, float* g_c, float* g_t, float* beta_t, float* wfix, float* S, float* Y,
+                  hipStream_t s);
+  int n() const { return dv_.n; }
+  int nv() const { return dv_.nv; }
 
   bool done() const { return loop_.done(); }
   const std::string& reason() const { return loop_.reason(); }

@@ -39,6 +39,12 @@ class WideBatchFitter {
   // features and the intercepts are written (synchronous).
   void current(float* w_out, hipStream_t s);
   void read_std(float* std_out, hipStream_t s);  // [U]
+  // Copies of the optimiser's vectors into caller-owned device buffers (nullptr: skip):
+  // x, d, g_c, g_t, beta_t, wfix are [nv], S and Y [hist][nv].  Synchronous, read-only.
+  void read_state(float* x, float* d, float* g_c, float* g_t, float* beta_t, float* wfix, float* S, float* Y,
+                  hipStream_t s);
+  int n() const { return dv_.n; }  // 0 before set_data
+  int nv() const { return dv_.nv; }
   // Device-event milliseconds of one evaluation at the current trial point, by stage:
   // row pass, column pass, reduction (tools/bench_wide_fit.py).  raw = 1: the reduction
   // of loss_grad (gradient only); raw = 0: the reduction of a fit's evaluation, which

@@ -189,4 +189,20 @@ void WideBatchFitter::read_std(float* std_out, hipStream_t s) {
   hip_check(hipStreamSynchronize(s), "hipStreamSynchronize(std)");
 }
 
+void WideBatchFitter::read_state(float* x, float* d, float* g_c, float* g_t, float* beta_t, float* wfix, float* S,
+                                 float* Y, hipStream_t s) {
+  if (!ws_) throw std::runtime_error("read_state: no dataset (set_data first)");
+  const size_t nv = (size_t)dv_.nv, H = (size_t)dv_.H;
+  const struct {
+    float* dst;
+    const float* src;
+    size_t words;
+  } parts[] = {{x, dv_.x, nv},           {d, dv_.d, nv},       {g_c, dv_.g_c, nv}, {g_t, dv_.g_t, nv},
+               {beta_t, dv_.beta_t, nv}, {wfix, dv_.wfix, nv}, {S, dv_.S, H * nv}, {Y, dv_.Y, H * nv}};
+  for (const auto& p : parts)
+    if (p.dst)
+      hip_check(hipMemcpyAsync(p.dst, p.src, p.words * 4, hipMemcpyDeviceToDevice, s), "hipMemcpyAsync(fit state)");
+  hip_check(hipStreamSynchronize(s), "hipStreamSynchronize(fit state)");
+}
+
 }  // namespace psx
