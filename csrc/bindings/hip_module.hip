@@ -327,25 +327,18 @@ PYBIND11_MODULE(_psx_hip, m) {
       py::arg("oor") = 0, py::arg("stream") = 0, py::arg("hist") = 0, py::arg("hist_form") = 0);
   // The form launch_score picks for the histogram by itself: 1 = LDS table, 2 = global atomics.
   m.def("score_hist_form", &score_hist_form, py::arg("FP"), py::arg("K"));
-  // Full-batch trainer (psx/ops/fit.py): the host loop of a fit runs with the GIL released.
-  py::class_<BatchFitter>(m, "BatchFitter")
-      .def(py::init<int, int, int, int, int>(), py::arg("K"), py::arg("F"), py::arg("FP"), py::arg("hist") = 10,
-           py::arg("max_wg") = 0)
-      .def(
-          "set_data",
-          [](BatchFitter& f, uintptr_t X, uintptr_t y, int64_t N, int64_t Npad, uintptr_t stream) {
-            f.set_data(P<const uint16_t>(X), P<const int32_t>(y), N, Npad, S(stream));
-          },
-          py::arg("X"), py::arg("y"), py::arg("N"), py::arg("Npad"), py::arg("stream") = 0)
+  // Full-batch trainers (psx/ops/fit.py, psx/ops/wide_fit.py): the lifecycle of a fit is bound once on
+  // the drivers' base; the host loop of a fit runs with the GIL released.
+  py::class_<FitDriver>(m, "FitDriver")
       .def(
           "loss_grad",
-          [](BatchFitter& f, uintptr_t w, uintptr_t grad, uintptr_t stream) {
+          [](FitDriver& f, uintptr_t w, uintptr_t grad, uintptr_t stream) {
             return f.loss_grad(P<const float>(w), P<float>(grad), S(stream));
           },
           py::arg("w"), py::arg("grad"), py::arg("stream") = 0)
       .def(
           "begin",
-          [](BatchFitter& f, uintptr_t w0, int max_iter, double tol, double reg_param, int ls_max, bool zero_const,
+          [](FitDriver& f, uintptr_t w0, int max_iter, double tol, double reg_param, int ls_max, bool zero_const,
              uintptr_t stream) {
             FitOpts o;
             o.max_iter = max_iter;
@@ -359,41 +352,49 @@ PYBIND11_MODULE(_psx_hip, m) {
           py::arg("zero_const") = true, py::arg("stream") = 0)
       .def(
           "run",
-          [](BatchFitter& f, int max_accept, uintptr_t stream) {
+          [](FitDriver& f, int max_accept, uintptr_t stream) {
             py::gil_scoped_release nogil;
             return f.run(max_accept, S(stream));
           },
           py::arg("max_accept"), py::arg("stream") = 0)
       .def(
-          "current", [](BatchFitter& f, uintptr_t w_out, uintptr_t stream) { f.current(P<float>(w_out), S(stream)); },
+          "current", [](FitDriver& f, uintptr_t w_out, uintptr_t stream) { f.current(P<float>(w_out), S(stream)); },
           py::arg("w_out"), py::arg("stream") = 0)
       .def(
-          "read_std", [](BatchFitter& f, uintptr_t out, uintptr_t stream) { f.read_std(P<float>(out), S(stream)); },
-          py::arg("out"), py::arg("stream") = 0)
-      .def(
           "read_state",
-          [](BatchFitter& f, uintptr_t x, uintptr_t d, uintptr_t g_c, uintptr_t g_t, uintptr_t beta_t, uintptr_t wfix,
+          [](FitDriver& f, uintptr_t x, uintptr_t d, uintptr_t g_c, uintptr_t g_t, uintptr_t beta_t, uintptr_t wfix,
              uintptr_t Sh, uintptr_t Yh, uintptr_t stream) {
             f.read_state(P<float>(x), P<float>(d), P<float>(g_c), P<float>(g_t), P<float>(beta_t), P<float>(wfix),
                          P<float>(Sh), P<float>(Yh), S(stream));
           },
           py::arg("x") = 0, py::arg("d") = 0, py::arg("g_c") = 0, py::arg("g_t") = 0, py::arg("beta_t") = 0,
           py::arg("wfix") = 0, py::arg("S") = 0, py::arg("Y") = 0, py::arg("stream") = 0)
-      .def_property_readonly("n", &BatchFitter::n)
-      .def_property_readonly("nv", &BatchFitter::nv)
-      .def_property_readonly("done", &BatchFitter::done)
-      .def_property_readonly("reason", &BatchFitter::reason)
-      .def_property_readonly("evals", &BatchFitter::evals)
-      .def_property_readonly("accepted", &BatchFitter::accepted)
-      .def_property_readonly("ls_fail", &BatchFitter::ls_fail)
-      .def_property_readonly("dir_reset", &BatchFitter::dir_reset)
-      .def_property_readonly("objective", &BatchFitter::objective)
-      .def_property_readonly("log_loss", &BatchFitter::log_loss)
-      .def_property_readonly("history", &BatchFitter::history)
-      .def_property_readonly("eval_seconds", &BatchFitter::eval_seconds)
-      .def_property_readonly("grid", &BatchFitter::grid);
-  // Full-batch trainer of the wide model (psx/ops/wide_fit.py)
-  py::class_<WideBatchFitter>(m, "WideBatchFitter")
+      .def_property_readonly("n", &FitDriver::n)
+      .def_property_readonly("nv", &FitDriver::nv)
+      .def_property_readonly("done", &FitDriver::done)
+      .def_property_readonly("reason", &FitDriver::reason)
+      .def_property_readonly("evals", &FitDriver::evals)
+      .def_property_readonly("accepted", &FitDriver::accepted)
+      .def_property_readonly("ls_fail", &FitDriver::ls_fail)
+      .def_property_readonly("dir_reset", &FitDriver::dir_reset)
+      .def_property_readonly("objective", &FitDriver::objective)
+      .def_property_readonly("log_loss", &FitDriver::log_loss)
+      .def_property_readonly("history", &FitDriver::history)
+      .def_property_readonly("eval_seconds", &FitDriver::eval_seconds)
+      .def_property_readonly("grid", &FitDriver::grid);
+  py::class_<BatchFitter, FitDriver>(m, "BatchFitter")
+      .def(py::init<int, int, int, int, int>(), py::arg("K"), py::arg("F"), py::arg("FP"), py::arg("hist") = 10,
+           py::arg("max_wg") = 0)
+      .def(
+          "set_data",
+          [](BatchFitter& f, uintptr_t X, uintptr_t y, int64_t N, int64_t Npad, uintptr_t stream) {
+            f.set_data(P<const uint16_t>(X), P<const int32_t>(y), N, Npad, S(stream));
+          },
+          py::arg("X"), py::arg("y"), py::arg("N"), py::arg("Npad"), py::arg("stream") = 0)
+      .def(
+          "read_std", [](BatchFitter& f, uintptr_t out, uintptr_t stream) { f.read_std(P<float>(out), S(stream)); },
+          py::arg("out"), py::arg("stream") = 0);
+  py::class_<WideBatchFitter, FitDriver>(m, "WideBatchFitter")
       .def(py::init<int, int, int, int>(), py::arg("K"), py::arg("KP"), py::arg("hist") = 10, py::arg("max_wg") = 0)
       .def(
           "set_data",
@@ -428,37 +429,6 @@ PYBIND11_MODULE(_psx_hip, m) {
           py::arg("short_items"), py::arg("long_items"), py::arg("N"), py::arg("U"), py::arg("F"),
           py::arg("n_items"), py::arg("n_short"), py::arg("n_long"), py::arg("stream") = 0)
       .def(
-          "loss_grad",
-          [](WideBatchFitter& f, uintptr_t w, uintptr_t grad, uintptr_t stream) {
-            return f.loss_grad(P<const float>(w), P<float>(grad), S(stream));
-          },
-          py::arg("w"), py::arg("grad"), py::arg("stream") = 0)
-      .def(
-          "begin",
-          [](WideBatchFitter& f, uintptr_t w0, int max_iter, double tol, double reg_param, int ls_max,
-             bool zero_const, uintptr_t stream) {
-            FitOpts o;
-            o.max_iter = max_iter;
-            o.tol = tol;
-            o.reg_param = reg_param;
-            o.ls_max = ls_max;
-            o.zero_const = zero_const ? 1 : 0;
-            f.begin(P<const float>(w0), o, S(stream));
-          },
-          py::arg("w0"), py::arg("max_iter"), py::arg("tol"), py::arg("reg_param"), py::arg("ls_max"),
-          py::arg("zero_const") = true, py::arg("stream") = 0)
-      .def(
-          "run",
-          [](WideBatchFitter& f, int max_accept, uintptr_t stream) {
-            py::gil_scoped_release nogil;
-            return f.run(max_accept, S(stream));
-          },
-          py::arg("max_accept"), py::arg("stream") = 0)
-      .def(
-          "current",
-          [](WideBatchFitter& f, uintptr_t w_out, uintptr_t stream) { f.current(P<float>(w_out), S(stream)); },
-          py::arg("w_out"), py::arg("stream") = 0)
-      .def(
           "read_std",
           [](WideBatchFitter& f, uintptr_t out, uintptr_t stream) { f.read_std(P<float>(out), S(stream)); },
           py::arg("out"), py::arg("stream") = 0)
@@ -468,29 +438,7 @@ PYBIND11_MODULE(_psx_hip, m) {
             py::gil_scoped_release nogil;
             return f.stage_ms(raw ? 1 : 0, S(stream));
           },
-          py::arg("raw"), py::arg("stream") = 0)
-      .def(
-          "read_state",
-          [](WideBatchFitter& f, uintptr_t x, uintptr_t d, uintptr_t g_c, uintptr_t g_t, uintptr_t beta_t, uintptr_t wfix,
-             uintptr_t Sh, uintptr_t Yh, uintptr_t stream) {
-            f.read_state(P<float>(x), P<float>(d), P<float>(g_c), P<float>(g_t), P<float>(beta_t), P<float>(wfix),
-                         P<float>(Sh), P<float>(Yh), S(stream));
-          },
-          py::arg("x") = 0, py::arg("d") = 0, py::arg("g_c") = 0, py::arg("g_t") = 0, py::arg("beta_t") = 0,
-          py::arg("wfix") = 0, py::arg("S") = 0, py::arg("Y") = 0, py::arg("stream") = 0)
-      .def_property_readonly("n", &WideBatchFitter::n)
-      .def_property_readonly("nv", &WideBatchFitter::nv)
-      .def_property_readonly("done", &WideBatchFitter::done)
-      .def_property_readonly("reason", &WideBatchFitter::reason)
-      .def_property_readonly("evals", &WideBatchFitter::evals)
-      .def_property_readonly("accepted", &WideBatchFitter::accepted)
-      .def_property_readonly("ls_fail", &WideBatchFitter::ls_fail)
-      .def_property_readonly("dir_reset", &WideBatchFitter::dir_reset)
-      .def_property_readonly("objective", &WideBatchFitter::objective)
-      .def_property_readonly("log_loss", &WideBatchFitter::log_loss)
-      .def_property_readonly("history", &WideBatchFitter::history)
-      .def_property_readonly("eval_seconds", &WideBatchFitter::eval_seconds)
-      .def_property_readonly("grid", &WideBatchFitter::grid);
+          py::arg("raw"), py::arg("stream") = 0);
   m.attr("wide_fit_short") = kWideFitShort;
   m.attr("wide_fit_reduce_cap") = kWideReduceMaxWG * 256;  // elements of one trip of the wide reduction
   m.def(

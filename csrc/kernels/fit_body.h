@@ -1,8 +1,9 @@
 // Device bodies shared by the dense fit kernels (fit_kernels.hip) and the wide ones
 // (wide_fit_kernels.hip): what does not depend on the weight layout.  fit_dots_body
 // turns the reduce workgroups' partial dots and the evaluation's loss partials into
-// the pinned result block; fit_update_body applies one controller action to element
-// e of the solver vectors and hands the new trial value to the layout's writer.
+// the pinned result block; fit_update_body (fit_step.h, also built for the host)
+// applies one controller action to element e of the solver vectors and hands the new
+// trial value to the layout's writer.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -37,38 +38,6 @@ __device__ __forceinline__ void fit_dots_body(const double* __restrict__ dpart, 
     out[kFitOutF] = loss + 0.5 * reg * bb;
     out[kFitOutLoss] = loss;
   }
-}
-
-// One controller action on element e.  x + t d is formed in fp64 and rounded once,
-// identically for the trial point and for the accepted iterate, so the accepted x is
-// exactly the point that was evaluated.
-template <class Dev, class WriteTrial>
-__device__ __forceinline__ void fit_update_body(const Dev& dv, const FitStep& st, int e, WriteTrial&& write_trial) {
-  float x = dv.x[e], d = dv.d[e];
-  if (st.action == kActInit) {
-    const float gc = dv.g_t[e];
-    dv.g_c[e] = gc;
-    d = (float)(st.cg * (double)gc);
-    dv.d[e] = d;
-  } else if (st.action == kActAccept || st.action == kActAcceptDone) {
-    x = (float)((double)x + st.t_acc * (double)d);
-    dv.x[e] = x;
-    if (st.action == kActAccept) {
-      const float gt = dv.g_t[e], gc = dv.g_c[e];
-      if (st.push_slot >= 0) {
-        dv.S[(size_t)st.push_slot * dv.nv + e] = (float)(st.t_acc * (double)d);
-        dv.Y[(size_t)st.push_slot * dv.nv + e] = gt - gc;
-      }
-      dv.g_c[e] = gt;
-      double nd = st.cg * (double)gt;
-      for (int i = 0; i < dv.H; ++i)  // (this thread alone wrote element e of the pushed pair)
-        nd += st.cs[i] * (double)dv.S[(size_t)i * dv.nv + e] + st.cy[i] * (double)dv.Y[(size_t)i * dv.nv + e];
-      d = (float)nd;
-      dv.d[e] = d;
-    }
-  }
-  if (st.action == kActInit || st.action == kActTrial || st.action == kActAccept)
-    write_trial(e, (float)((double)x + st.t * (double)d));
 }
 
 }  // namespace psx

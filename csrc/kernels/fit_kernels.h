@@ -7,14 +7,9 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
-#include "solver_ctrl.h"
+#include "fit_step.h"  // FitStep, the result block's layout
 
 namespace psx {
-
-constexpr int kFitDotStride = 40;  // per-workgroup partial dots: num_dots(kMaxHist) + ||beta||^2, padded
-// host block of one evaluation: f_t, mean cross entropy, then the dots in num_dots(hist) layout
-constexpr int kFitOutF = 0, kFitOutLoss = 1, kFitOutDots = 2;
-constexpr int kFitOutWords = kFitOutDots + 3 + 2 * kMaxHist + 1;
 
 // Vectors of the fit: n = K*FP + K elements in the model's device layout
 // ([K][FP] coefficients, then K intercepts); the curvature pairs have stride nv.
@@ -35,13 +30,6 @@ struct FitDev {
   double* spart;                      // [G][2][FP] per-workgroup column sums / sums of squares
   double* dpart;                      // [reduce workgroups][kFitDotStride]
   double* out;                        // [kFitOutWords]
-};
-
-// One controller action for fit_update (Action of solver_ctrl.h).
-struct FitStep {
-  int action, push_slot;
-  double t, t_acc, cg;
-  double cs[kMaxHist], cy[kMaxHist];
 };
 
 void prepare_fit_kernels();

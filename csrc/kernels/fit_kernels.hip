@@ -243,7 +243,7 @@ __global__ __launch_bounds__(256) void fit_dots_kernel(FitDev dv, int NB, int nf
 }
 
 // ---------------------------------------------------------------------------
-// One controller action on the vectors (fit_update_body of fit_body.h).
+// One controller action on the vectors (fit_update_body of fit_step.h).
 __global__ __launch_bounds__(256) void fit_update_kernel(FitDev dv, FitStep st) {
   const int e = blockIdx.x * 256 + threadIdx.x;
   if (e >= dv.n) return;

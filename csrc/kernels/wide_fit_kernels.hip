@@ -24,7 +24,7 @@
 //   wide_fit_bsum_kernel  the W residual-sum partials -> the intercept gradient
 //   wide_fit_reduce       a column's items summed in chunk order,
 //                         g_t = sum / N / sigma + reg * beta_t, partial fp64 dots
-//   fit_dots_body / fit_update_body of fit_body.h: f_t and the dots, one controller
+//   fit_dots_body (fit_body.h) / fit_update_body (fit_step.h): f_t and the dots, one controller
 //                         action -- the dense fit's arithmetic.
 // Every sum runs in an order fixed by the data and the options (col_chunk, max_wg):
 // a fit is bit-reproducible.  No atomics, no cross-workgroup waits.

@@ -2,8 +2,9 @@
 // (fit.hip) and the wide one (wide_fit.hip): evaluate, run the HOST build of
 // solver_ctrl.h's ctrl_step on (f_t, dots), keep the objective history, hand the
 // resulting action to the fitter and name the termination reason.  It launches
-// nothing itself: a fitter supplies "evaluate" (fills the pinned result block of
-// fit_kernels.h) and "apply step" (launches its update kernel).
+// nothing itself and includes nothing of HIP (csrc/tests/host_selftest.cc runs it on
+// the CPU): the caller supplies "evaluate" (fills the result block of fit_step.h) and
+// "apply step" (FitDriver of fit_driver.h launches the fitter's update kernel).
 #pragma once
 #include <climits>
 #include <cmath>
@@ -11,7 +12,7 @@
 #include <string>
 #include <vector>
 
-#include "../kernels/fit_kernels.h"
+#include "../kernels/fit_step.h"
 
 namespace psx {
 

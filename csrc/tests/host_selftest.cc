@@ -15,7 +15,9 @@
 //   a real tracker, real windows, a real metrics sink and real token queues with a
 //   scripted plane (release records, tokens) and a scripted clock,
 //   ShardFeed + RoundGate (the producer feed and the BSP round wait of the native loops)
-//   over real windows with a scripted clock.
+//   over real windows with a scripted clock,
+//   FitLoop + fit_update_body (the controller loop of the full-batch fitters and their
+//   vector update) on a quadratic: every termination reason, stepping, the lifecycle errors.
 // Exit status 0 = all checks passed.
 #include <atomic>
 #include <chrono>
@@ -39,6 +41,7 @@
 #include "../host/sampling.h"
 #include "../host/server_protocol.h"
 #include "../host/tracker.h"
+#include "../solver/fit_loop.h"
 
 using namespace psx;
 
@@ -1493,6 +1496,153 @@ static void test_round_gate() {
   }
 }
 
+// ---- FitLoop (csrc/solver/fit_loop.h): the controller loop of a full-batch fit ----
+// A fitter in miniature on f(x) = 0.5 * sum a_i (x_i - c_i)^2: fp32 vectors as the
+// kernels keep them (stride nv > n, history 2), "evaluate" fills the result block in
+// fp64 as the reductions do, "apply" runs fit_update_body of fit_step.h per element.
+struct QuadFit {
+  int n = 3, nv = 4, H = 2;  // (the names fit_update_body reads)
+  float xs[4] = {}, ds[4] = {}, gcs[4] = {}, gts[4] = {}, bts[4] = {}, Ss[8] = {}, Ys[8] = {};
+  float *x = xs, *d = ds, *g_c = gcs, *g_t = gts, *beta_t = bts, *S = Ss, *Y = Ys;
+  double a[3] = {1e-5, 1e-4, 1e-3}, c[3] = {1.0, -2.0, 0.5};
+  double pin[kFitOutWords] = {};
+  bool nan_objective = false;
+  FitLoop loop;
+  QuadFit() = default;
+  QuadFit(const QuadFit&) = delete;
+
+  void begin(double off, const FitOpts& o) {  // start at c + off * (1, -1, 1)
+    for (int i = 0; i < n; ++i) x[i] = beta_t[i] = (float)(c[i] + (i == 1 ? -off : off));
+    loop.start(o, H);
+  }
+  void evaluate(double reg) {
+    double f = 0.0, bb = 0.0;
+    for (int i = 0; i < n; ++i) {
+      const double r = (double)beta_t[i] - c[i];
+      f += 0.5 * a[i] * r * r;
+      bb += (double)beta_t[i] * beta_t[i];
+      g_t[i] = (float)(a[i] * r + reg * beta_t[i]);
+    }
+    double* dots = pin + kFitOutDots;  // num_dots(H) dots, then ||beta||^2
+    for (int k = 0; k <= num_dots(H); ++k) dots[k] = 0.0;
+    for (int i = 0; i < n; ++i) {
+      const double g = g_t[i];
+      dots[0] += g * g;
+      dots[1] += g * d[i];
+      dots[2] += g * g_c[i];
+      for (int h = 0; h < H; ++h) {
+        dots[3 + h] += (double)S[h * nv + i] * g;
+        dots[3 + H + h] += (double)Y[h * nv + i] * g;
+      }
+    }
+    dots[num_dots(H)] = bb;
+    pin[kFitOutLoss] = f;
+    pin[kFitOutF] = nan_objective ? std::nan("") : f + 0.5 * reg * bb;
+  }
+  bool run(int max_accept) {
+    return loop.run(
+        max_accept, pin, [&](double reg) { evaluate(reg); },
+        [&](const FitStep& st) {
+          for (int e = 0; e < n; ++e) fit_update_body(*this, st, e, [&](int i, float bt) { beta_t[i] = bt; });
+        });
+  }
+};
+
+static void test_fit_loop() {
+  FitOpts o;
+  o.max_iter = 50;
+  o.tol = 1e-3;
+  std::vector<double> whole;
+  {  // a converging run: ends by a tolerance test within the budget, the objective falls at every accepted step
+    QuadFit q;
+    q.begin(1000.0, o);
+    CHECK(q.run(1 << 30) && q.loop.done() && q.loop.reason() == "tol");
+    const Ctrl& k = q.loop.ctrl();
+    const std::vector<double>& h = q.loop.history();
+    CHECK(k.nacc > q.H + 1 && k.nacc < o.max_iter && k.evals >= k.nacc + 1);  // the ring of 2 pairs wrapped
+    CHECK((int)h.size() == k.nacc + 1 && h.back() == k.f_c);
+    for (size_t i = 1; i < h.size(); ++i) CHECK(h[i] < h[i - 1]);
+    // "tol" is ctrl_accept's done = gnorm <= tol * fscale || |f_prev - f_t| <= tol * fscale with
+    // fscale = max(1, |f_t|), gnorm^2 = dots[0] = sum g_t_i^2 over the fp32 gradient the evaluation
+    // stored.  The inputs are chosen so that the gradient test is the one that fires (a_i <= tol: near the
+    // minimum f = 0.5 sum g_i^2 / a_i still falls by more than tol a step when |g| is already below it);
+    // both tests are re-evaluated here.  The accepted x is exactly the evaluated point,
+    // so g_t is still the gradient at x: |g_t_i| <= gnorm <= tol * fscale.  g_t_i is the fp32 rounding of
+    // a_i (x_i - c_i) formed in fp64, hence a_i |x_i - c_i| <= |g_t_i| (1 + 2^-23) (the fp32 rounding is
+    // 2^-24 relative, the two fp64 roundings 2^-53 each), and
+    //   |x_i - c_i| <= tol * fscale * (1 + 2^-23) / a_i.
+    const double fscale = std::fabs(h.back()) > 1.0 ? std::fabs(h.back()) : 1.0, lim = (double)(float)o.tol * fscale;
+    double tt = 0.0;
+    for (int i = 0; i < q.n; ++i) tt += (double)q.g_t[i] * q.g_t[i];
+    CHECK(std::sqrt(tt) <= lim && !(std::fabs(h[h.size() - 2] - h.back()) <= lim));
+    for (int i = 0; i < q.n; ++i) {
+      CHECK(q.x[i] == q.beta_t[i]);
+      CHECK(std::fabs((double)q.x[i] - q.c[i]) <= lim * (1.0 + std::ldexp(1.0, -23)) / q.a[i]);
+    }
+    whole = h;
+  }
+  {  // the same fit one accepted step per call: false until the last call, which returns true
+    QuadFit q;
+    q.begin(1000.0, o);
+    const int last = (int)whole.size() - 1;
+    for (int it = 1; it <= last; ++it) {
+      CHECK(q.run(1) == (it == last));
+      CHECK(q.loop.ctrl().nacc == it && q.loop.done() == (it == last));
+    }
+    CHECK(q.loop.reason() == "tol" && q.loop.history() == whole);
+    CHECK(q.run(1) && q.loop.ctrl().nacc == last);  // an ended fit evaluates nothing more
+  }
+  {  // no iteration allowed: the start is evaluated once and is the result
+    QuadFit q;
+    FitOpts z = o;
+    z.max_iter = 0;
+    q.begin(1000.0, z);
+    CHECK(q.run(1 << 30) && q.loop.reason() == "max_iter");
+    CHECK(q.loop.ctrl().evals == 1 && q.loop.ctrl().nacc == 0 && q.loop.history().size() == 1);
+  }
+  {  // one iteration allowed: exactly one accepted step
+    QuadFit q;
+    FitOpts z = o;
+    z.max_iter = 1;
+    q.begin(1000.0, z);
+    CHECK(q.run(1 << 30) && q.loop.reason() == "max_iter");
+    CHECK(q.loop.ctrl().nacc == 1 && q.loop.history().size() == 2 && q.loop.history()[1] < q.loop.history()[0]);
+  }
+  {  // a NaN objective at the start
+    QuadFit q;
+    q.nan_objective = true;
+    q.begin(1000.0, o);
+    CHECK(q.run(1 << 30) && q.loop.reason() == "no_descent");
+    CHECK(q.loop.ctrl().evals == 1 && q.loop.ctrl().nacc == 0);
+  }
+  {  // a line search of one evaluation whose first trial overshoots.  The first step is x - g / ||g||, of
+    // length 1; 0.001 away from c in every coordinate that is far past the minimum along -g: phi(t) =
+    // f - t ||g||^2 + 0.5 t^2 g'Ag rises at t = 1 / ||g|| once 0.5 g'Ag / ||g||^2 (>= 0.5 a_min = 5e-6)
+    // exceeds ||g|| (<= a_max * 0.001 * sqrt(3) < 2e-6), so sufficient decrease fails
+    QuadFit q;
+    FitOpts z = o;
+    z.ls_max = 1;
+    q.begin(0.001, z);
+    CHECK(q.run(1 << 30) && q.loop.reason() == "line_search");
+    CHECK(q.loop.ctrl().evals == 2 && q.loop.ctrl().nacc == 0 && q.loop.ctrl().ls_fail == 1);
+    CHECK(q.loop.history().size() == 1);
+  }
+  {  // run without a fit in progress: before start, and after stop (a new dataset, a single evaluation)
+    QuadFit q;
+    CHECK(error_of<std::runtime_error>([&] { q.run(1); }) == "fit: begin() first");
+    q.begin(1000.0, o);
+    CHECK(!q.run(1) && !q.loop.done());
+    q.loop.stop();
+    CHECK(q.loop.done() && !q.loop.begun());
+    CHECK(error_of<std::runtime_error>([&] { q.run(1); }) == "fit: begin() first");
+    CHECK(error_of<std::invalid_argument>([&] {
+            FitOpts bad = o;
+            bad.ls_max = 0;
+            q.loop.start(bad, q.H);
+          }) == "fit: bad max_iter / ls_max / tol");
+  }
+}
+
 int main() {
   test_tracker();
   test_tracker_faults();
@@ -1505,6 +1655,7 @@ int main() {
   test_lanes_protocol();
   test_shard_feed();
   test_round_gate();
+  test_fit_loop();
   if (g_fail) {
     std::fprintf(stderr, "%d check(s) failed\n", g_fail);
     return 1;

@@ -187,14 +187,15 @@ class _Resident:
         self.y[:n] = ds.y.to(device, torch.int32)
 
 
-class BatchFitter:
-    """Full-batch L-BFGS trainer of one dense model on one device.
+class _FitterBase:
+    """What the dense and the wide trainer share: one native fitter per object, the
+    resident dataset, :meth:`fit`, :meth:`loss_grad` and the GPU path of both.  A
+    subclass supplies ``_check_spec`` / ``_check_data``, ``_new_native``, ``_load``,
+    ``_result_vector``, ``_std_features`` and its CPU paths (``_fit_cpu``,
+    ``_loss_grad_cpu``)."""
 
-    ``fit`` may be called any number of times (each call loads its dataset); no
-    state of one fit reaches the next."""
-
-    def __init__(self, spec: ModelSpec, device, opts: FitOptions | None = None):
-        _check_spec(spec)
+    def __init__(self, spec, device, opts: FitOptions | None = None):
+        self._check_spec(spec)
         self.spec = spec
         self.device = torch.device(device)
         self.opts = opts or FitOptions()
@@ -202,29 +203,24 @@ class BatchFitter:
         self._native = None
         if is_gpu(self.device):
             with torch.cuda.device(self.device):
-                self._native = _native.hip().BatchFitter(spec.K, spec.F, spec.Fp, self.opts.hist,
-                                                         self.opts.max_wg or 0)
+                self._native = self._new_native(_native.hip())
         self._data = None
 
     # ---- one evaluation ------------------------------------------------------
-    def loss_grad(self, ds: Dataset, w: torch.Tensor):
-        """Mean cross entropy of ``w`` (device layout) over ``ds`` and its gradient
-        in the same layout: original feature space, no standardisation, no penalty.
-        Calls in a row with the same ``ds`` object reuse its resident copy (and skip
-        the checks): do not change its tensors in between."""
+    def loss_grad(self, ds, w: torch.Tensor):
+        """Mean loss of ``w`` (device layout ``[P]``) over ``ds`` and its gradient in
+        the same layout (zero for every feature a sparse ``ds`` does not touch):
+        original feature space, no standardisation, no penalty.  Calls in a row with
+        the same ``ds`` object reuse its resident copy (and skip the checks): do not
+        change its tensors in between."""
         s = self.spec
         resident = self._data is not None and self._data.src is ds
         if not resident:
-            _check_data(s, ds, 1)
+            self._check_data(s, ds, 1)
         if w.numel() != s.P:
             raise ValueError(f"the model has {s.P} weights in device layout, got {w.numel()}")
         if self._native is None:
-            from ..models.reference import multinomial_loss_grad
-
-            X = ds.X[:, : s.F].to(torch.bfloat16).double().cpu()
-            wc = w.detach().double().cpu()
-            loss, gc, gb = multinomial_loss_grad(X, ds.y.long().cpu(), s.coef(wc), s.intercept(wc))
-            return float(loss), s.pack(gc, gb, device=self.device)
+            return self._loss_grad_cpu(ds, w, resident)
         with torch.cuda.device(self.device):
             if not resident:
                 self._load(ds)
@@ -233,25 +229,19 @@ class BatchFitter:
             loss = self._native.loss_grad(wd.data_ptr(), g.data_ptr(), stream_handle(self.device))
         return float(loss), g
 
-    def _load(self, ds: Dataset) -> _Resident:
-        data = _Resident(ds, self.device)
-        self._native.set_data(data.X.data_ptr(), data.y.data_ptr(), data.N, data.Npad, stream_handle(self.device))
-        self._data = data  # the native fitter reads these buffers until the next set_data
-        return data
-
     # ---- the fit ---------------------------------------------------------------
-    def fit(self, train: Dataset, w0: torch.Tensor | None = None, valid: Dataset | None = None,
-            valid_every: int = 1, patience: int | None = None) -> FitResult:
+    def fit(self, train, w0: torch.Tensor | None = None, valid=None, valid_every: int = 1,
+            patience: int | None = None) -> FitResult:
         """Fit ``train`` from zeros or from ``w0`` (device layout, a warm start).
 
         With ``valid`` the current iterate is scored with :class:`Scorer` every
         ``valid_every`` accepted iterations; the result carries the iterate with the
         lowest validation log-loss, and ``patience`` checks in a row without
         improvement end the fit with reason ``early_stop``."""
-        s, o = self.spec, self.opts
-        _check_data(s, train, 2)
+        s = self.spec
+        self._check_data(s, train, 2)
         if valid is not None:
-            _check_data(s, valid, 1)
+            self._check_data(s, valid, 1)
             if valid_every < 1 or (patience is not None and patience < 1):
                 raise ValueError("valid_every and patience must be >= 1")
         if w0 is not None and w0.numel() != s.P:
@@ -278,26 +268,62 @@ class BatchFitter:
     def _fit_gpu(self, train, w0, valid, valid_every, patience) -> FitResult:
         s, o, nat, dev = self.spec, self.opts, self._native, self.device
         st = stream_handle(dev)
-        self._load(train)
+        data = self._load(train)
         w0d = None
         if w0 is not None:
             w0d = w0.detach().to(dev, torch.float32).reshape(-1).contiguous()
         nat.begin(w0d.data_ptr() if w0d is not None else 0, int(o.max_iter), float(o.tol), float(o.reg_param),
                   int(o.ls_max), bool(o.zero_const), st)
-        w = torch.empty(s.P, dtype=torch.float32, device=dev)
+        w = self._result_vector(w0)
         check = self._validator(valid) if valid is not None else None
         best, vhist, reason = _run_native(nat, st, w, check, valid_every, patience)
-        std = torch.empty(s.Fp, dtype=torch.float32, device=dev)
-        nat.read_std(std.data_ptr(), st)
+        std, features = self._std_features(data, st)
         ev = list(nat.eval_seconds)
         res = FitResult(spec=s, w=w, objective=float(nat.objective), log_loss=float(nat.log_loss),
                         history=list(nat.history), iters=int(nat.accepted), evals=int(nat.evals),
-                        reason=reason or str(nat.reason), std=std[: s.F].clone(), seconds=0.0,
+                        reason=reason or str(nat.reason), std=std, seconds=0.0,
                         pass_seconds=statistics.median(ev) if ev else 0.0, options=o, valid_history=vhist,
-                        ls_fail=int(nat.ls_fail))
+                        ls_fail=int(nat.ls_fail), features=features)
         if best is not None:
             res.w, res.best_iter, res.objective, res.log_loss = best[2], best[1], best[3], best[4]
         return res
+
+
+class BatchFitter(_FitterBase):
+    """Full-batch L-BFGS trainer of one dense model on one device.
+
+    ``fit`` may be called any number of times (each call loads its dataset); no
+    state of one fit reaches the next."""
+
+    _check_spec = staticmethod(_check_spec)
+    _check_data = staticmethod(_check_data)
+
+    def _new_native(self, hip):
+        s = self.spec
+        return hip.BatchFitter(s.K, s.F, s.Fp, self.opts.hist, self.opts.max_wg or 0)
+
+    def _load(self, ds: Dataset) -> _Resident:
+        data = _Resident(ds, self.device)
+        self._native.set_data(data.X.data_ptr(), data.y.data_ptr(), data.N, data.Npad, stream_handle(self.device))
+        self._data = data  # the native fitter reads these buffers until the next set_data
+        return data
+
+    def _result_vector(self, w0):
+        return torch.empty(self.spec.P, dtype=torch.float32, device=self.device)  # finalize writes all of it
+
+    def _std_features(self, data, st):
+        std = torch.empty(self.spec.Fp, dtype=torch.float32, device=self.device)
+        self._native.read_std(std.data_ptr(), st)
+        return std[: self.spec.F].clone(), None
+
+    def _loss_grad_cpu(self, ds, w, resident):
+        from ..models.reference import multinomial_loss_grad
+
+        s = self.spec
+        X = ds.X[:, : s.F].to(torch.bfloat16).double().cpu()
+        wc = w.detach().double().cpu()
+        loss, gc, gb = multinomial_loss_grad(X, ds.y.long().cpu(), s.coef(wc), s.intercept(wc))
+        return float(loss), s.pack(gc, gb, device=self.device)
 
     def _fit_cpu(self, train, w0, valid, valid_every, patience) -> FitResult:
         s, o = self.spec, self.opts

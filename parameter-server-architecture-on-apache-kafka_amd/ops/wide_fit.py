@@ -21,7 +21,6 @@ matrix over the touched columns and its transpose); no ``N x F`` matrix is built
 """
 from __future__ import annotations
 
-import statistics
 import time
 import warnings
 
@@ -30,8 +29,8 @@ import torch
 from .. import _native
 from ..models.reference import fit_reference
 from ..models.wide import WideSpec
-from .fit import FitOptions, FitResult, _check_options, _run_native, _validate_oracle
-from .lr import is_gpu, stream_handle
+from .fit import FitOptions, FitResult, _FitterBase, _validate_oracle
+from .lr import stream_handle
 from .sparse import SparseDataset
 
 # Entries of a work item of the column pass.  The rule of thumb for an atomics-free
@@ -160,8 +159,9 @@ def _closures(ix: _Index, K: int):
     return loss_grad, ((sq + (N - present) * mean * mean) / (N - 1)).clamp_min(0).sqrt()
 
 
-class WideFitter:
-    """Full-batch L-BFGS trainer of one wide model on one device.
+class WideFitter(_FitterBase):
+    """Full-batch L-BFGS trainer of one wide model on one device
+    (``fit`` / ``loss_grad`` / ``valid`` as :class:`psx.ops.fit.BatchFitter`).
 
     ``fit`` may be called any number of times (each call loads its dataset); no
     state of one fit reaches the next.  ``col_chunk`` (default 2048) is the length at
@@ -169,20 +169,17 @@ class WideFitter:
     one after the other, N / col_chunk of them for a column every row holds, so a
     small ``col_chunk`` on many rows (below N / 1000 or so) slows every evaluation."""
 
+    _check_spec = staticmethod(_check_spec)
+    _check_data = staticmethod(_check_data)
+
     def __init__(self, spec: WideSpec, device, opts: FitOptions | None = None, col_chunk: int | None = None):
-        _check_spec(spec)
-        self.spec = spec
-        self.device = torch.device(device)
-        self.opts = opts or FitOptions()
-        _check_options(self.opts)
+        super().__init__(spec, device, opts)
         self.col_chunk = DEFAULT_COL_CHUNK if col_chunk is None else int(col_chunk)
         if self.col_chunk < 1:
             raise ValueError(f"col_chunk must be >= 1, got {col_chunk}")
-        self._native = None
-        if is_gpu(self.device):
-            with torch.cuda.device(self.device):
-                self._native = _native.hip().WideBatchFitter(spec.K, spec.KP, self.opts.hist, self.opts.max_wg or 0)
-        self._data = None
+
+    def _new_native(self, hip):
+        return hip.WideBatchFitter(self.spec.K, self.spec.KP, self.opts.hist, self.opts.max_wg or 0)
 
     def _load(self, ds: SparseDataset):
         if self._native is None:
@@ -198,69 +195,6 @@ class WideFitter:
         self._data = d  # the native fitter reads these buffers until the next set_data
         return d
 
-    # ---- one evaluation ------------------------------------------------------
-    def loss_grad(self, ds: SparseDataset, w: torch.Tensor):
-        """Mean loss of ``w`` (device layout ``[P]``) over ``ds`` and its gradient in
-        the same layout (zero for every feature ``ds`` does not touch): original
-        feature space, no standardisation, no penalty.  Calls in a row with the same
-        ``ds`` object reuse its resident copy: do not change its tensors in between."""
-        s = self.spec
-        resident = self._data is not None and self._data.src is ds
-        if not resident:
-            _check_data(s, ds, 1)
-        if w.numel() != s.P:
-            raise ValueError(f"the model has {s.P} weights in device layout, got {w.numel()}")
-        if self._native is None:
-            d = self._data if resident else self._load(ds)
-            wc = w.detach().double().cpu().reshape(-1)
-            fg, _ = _closures(d, s.K)
-            rows = d.uniq.long()
-            ce = wc[: s.F * s.KP].view(s.F, s.KP)[rows][:, : s.K].t()
-            loss, gc, gb = fg(ce, s.intercept(wc))
-            g = torch.zeros(s.P, dtype=torch.float32, device=self.device)
-            g[: s.F * s.KP].view(s.F, s.KP)[rows, : s.K] = gc.t().float()
-            g[s.F * s.KP: s.F * s.KP + s.K] = gb.float()
-            return float(loss), g
-        with torch.cuda.device(self.device):
-            if not resident:
-                self._load(ds)
-            wd = w.detach().to(self.device, torch.float32).reshape(-1).contiguous()
-            g = torch.empty(s.P, dtype=torch.float32, device=self.device)
-            loss = self._native.loss_grad(wd.data_ptr(), g.data_ptr(), stream_handle(self.device))
-        return float(loss), g
-
-    # ---- the fit ---------------------------------------------------------------
-    def fit(self, train: SparseDataset, w0: torch.Tensor | None = None, valid: SparseDataset | None = None,
-            valid_every: int = 1, patience: int | None = None) -> FitResult:
-        """Fit ``train`` from zeros or from ``w0`` (device layout, a warm start);
-        ``valid`` / ``valid_every`` / ``patience`` as :meth:`psx.ops.fit.BatchFitter.fit`."""
-        s = self.spec
-        _check_data(s, train, 2)
-        if valid is not None:
-            _check_data(s, valid, 1)
-            if valid_every < 1 or (patience is not None and patience < 1):
-                raise ValueError("valid_every and patience must be >= 1")
-        if w0 is not None and w0.numel() != s.P:
-            raise ValueError(f"the model has {s.P} weights in device layout, got {w0.numel()}")
-        t0 = time.perf_counter()
-        if self._native is None:
-            res = self._fit_cpu(train, w0, valid, valid_every, patience)
-        else:
-            with torch.cuda.device(self.device):
-                res = self._fit_gpu(train, w0, valid, valid_every, patience)
-        res.seconds = time.perf_counter() - t0
-        return res
-
-    def _validator(self, valid):
-        from .score import Scorer
-
-        vds = valid.to(self.device)
-
-        def check(w):
-            return float(Scorer(self.spec, w, self.device).score(vds).log_loss)
-
-        return check
-
     def _untouched(self, w0):
         """The full vector before the touched features are written: zeros, or with
         ``zero_const=False`` the start's coefficients (centred like every excluded
@@ -274,29 +208,25 @@ class WideFitter:
             w[: s.F * s.KP].view(s.F, s.KP)[:, : s.K] = c
         return w
 
-    def _fit_gpu(self, train, w0, valid, valid_every, patience) -> FitResult:
-        s, o, nat, dev = self.spec, self.opts, self._native, self.device
-        st = stream_handle(dev)
-        d = self._load(train)
-        w0d = None
-        if w0 is not None:
-            w0d = w0.detach().to(dev, torch.float32).reshape(-1).contiguous()
-        nat.begin(w0d.data_ptr() if w0d is not None else 0, int(o.max_iter), float(o.tol), float(o.reg_param),
-                  int(o.ls_max), bool(o.zero_const), st)
-        w = self._untouched(w0)
-        check = self._validator(valid) if valid is not None else None
-        best, vhist, reason = _run_native(nat, st, w, check, valid_every, patience)
-        std = torch.empty(d.U, dtype=torch.float32, device=dev)
-        nat.read_std(std.data_ptr(), st)
-        ev = list(nat.eval_seconds)
-        res = FitResult(spec=s, w=w, objective=float(nat.objective), log_loss=float(nat.log_loss),
-                        history=list(nat.history), iters=int(nat.accepted), evals=int(nat.evals),
-                        reason=reason or str(nat.reason), std=std, seconds=0.0,
-                        pass_seconds=statistics.median(ev) if ev else 0.0, options=o, valid_history=vhist,
-                        ls_fail=int(nat.ls_fail), features=d.uniq.clone())
-        if best is not None:
-            res.w, res.best_iter, res.objective, res.log_loss = best[2], best[1], best[3], best[4]
-        return res
+    _result_vector = _untouched  # finalize writes the touched features and the intercepts
+
+    def _std_features(self, d, st):
+        std = torch.empty(d.U, dtype=torch.float32, device=self.device)
+        self._native.read_std(std.data_ptr(), st)
+        return std, d.uniq.clone()
+
+    def _loss_grad_cpu(self, ds, w, resident):
+        s = self.spec
+        d = self._data if resident else self._load(ds)
+        wc = w.detach().double().cpu().reshape(-1)
+        fg, _ = _closures(d, s.K)
+        rows = d.uniq.long()
+        ce = wc[: s.F * s.KP].view(s.F, s.KP)[rows][:, : s.K].t()
+        loss, gc, gb = fg(ce, s.intercept(wc))
+        g = torch.zeros(s.P, dtype=torch.float32, device=self.device)
+        g[: s.F * s.KP].view(s.F, s.KP)[rows, : s.K] = gc.t().float()
+        g[s.F * s.KP: s.F * s.KP + s.K] = gb.float()
+        return float(loss), g
 
     def _fit_cpu(self, train, w0, valid, valid_every, patience) -> FitResult:
         s, o = self.spec, self.opts
