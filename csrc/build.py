@@ -157,7 +157,8 @@ def build_selftest(sanitize: str = "address,undefined", force=False):
     sources = [os.path.join(CSRC, "tests", "host_selftest.cc")] + sorted(glob.glob(os.path.join(CSRC, "host", "*.cc")))
     headers = sorted(glob.glob(os.path.join(CSRC, "host", "*.h"))) + [
         os.path.join(CSRC, "kernels", "lanes_records.h"), os.path.join(CSRC, "kernels", "solver_ctrl.h"),
-        os.path.join(CSRC, "kernels", "fit_step.h"), os.path.join(CSRC, "solver", "fit_loop.h")]
+        os.path.join(CSRC, "kernels", "fit_step.h"), os.path.join(CSRC, "kernels", "dispatch.h"),
+        os.path.join(CSRC, "solver", "fit_loop.h")]
     tag = sanitize.replace(",", "_")
     out = os.path.join(ROOT, "build", "selftest", f"host_selftest_{tag}")
     flags = ["-O1", "-g", "-std=c++17", f"-fsanitize={sanitize}", "-fno-omit-frame-pointer"]

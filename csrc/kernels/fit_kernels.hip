@@ -18,6 +18,7 @@
 // order, butterflies): a fit is bit-reproducible.  No atomics at all.
 #include <hip/hip_runtime.h>
 
+#include "dispatch.h"
 #include "fit_body.h"
 #include "fit_kernels.h"
 #include "solve_body.h"
@@ -276,20 +277,13 @@ __global__ __launch_bounds__(256) void fit_finalize_kernel(FitDev dv, int center
 }
 
 // ---------------------------------------------------------------------------
-template <int FP>
-static void set_fit_lds_attr() {
-  (void)hipFuncSetAttribute((const void*)fit_lossgrad_kernel<FP>, hipFuncAttributeMaxDynamicSharedMemorySize,
-                            (int)eval_lds_bytes(FP));
-}
-
 void prepare_fit_kernels() {
   static bool done = false;
   if (done) return;
-  set_fit_lds_attr<128>();
-  set_fit_lds_attr<256>();
-  set_fit_lds_attr<512>();
-  set_fit_lds_attr<1024>();
-  set_fit_lds_attr<2048>();
+  for_each_fp([](auto fp) {
+    (void)hipFuncSetAttribute((const void*)fit_lossgrad_kernel<fp()>, hipFuncAttributeMaxDynamicSharedMemorySize,
+                              (int)eval_lds_bytes(fp()));
+  });
   done = true;
 }
 
@@ -297,14 +291,7 @@ int fit_reduce_grid(int n) { return (n + 63) / 64; }
 
 void launch_fit_stats(const FitDev& dv, int G, hipStream_t s) {
   const size_t lb = (size_t)256 * 16 * sizeof(double);
-  switch (dv.FP) {
-    case 128: fit_stats_kernel<128><<<G, 256, lb, s>>>(dv); break;
-    case 256: fit_stats_kernel<256><<<G, 256, lb, s>>>(dv); break;
-    case 512: fit_stats_kernel<512><<<G, 256, lb, s>>>(dv); break;
-    case 1024: fit_stats_kernel<1024><<<G, 256, lb, s>>>(dv); break;
-    case 2048: fit_stats_kernel<2048><<<G, 256, lb, s>>>(dv); break;
-    default: return;
-  }
+  dispatch_fp("fit: padded width", dv.FP, [&](auto fp) { fit_stats_kernel<fp()><<<G, 256, lb, s>>>(dv); });
   fit_stats_fin_kernel<<<(dv.FP + 255) / 256, 256, 0, s>>>(dv, G);
 }
 
@@ -327,14 +314,9 @@ void launch_fit_lossgrad(const FitDev& dv, int G, hipStream_t s) {
   sdv.wlo = dv.wlo;
   sdv.part = dv.part;
   const size_t lb = eval_lds_bytes(dv.FP);
-  switch (dv.FP) {
-    case 128: fit_lossgrad_kernel<128><<<G, 256, lb, s>>>(cfg, pr, sdv, dv.gpart); break;
-    case 256: fit_lossgrad_kernel<256><<<G, 256, lb, s>>>(cfg, pr, sdv, dv.gpart); break;
-    case 512: fit_lossgrad_kernel<512><<<G, 256, lb, s>>>(cfg, pr, sdv, dv.gpart); break;
-    case 1024: fit_lossgrad_kernel<1024><<<G, 256, lb, s>>>(cfg, pr, sdv, dv.gpart); break;
-    case 2048: fit_lossgrad_kernel<2048><<<G, 256, lb, s>>>(cfg, pr, sdv, dv.gpart); break;
-    default: break;
-  }
+  dispatch_fp("fit: padded width", dv.FP, [&](auto fp) {
+    fit_lossgrad_kernel<fp()><<<G, 256, lb, s>>>(cfg, pr, sdv, dv.gpart);
+  });
 }
 
 void launch_fit_reduce(const FitDev& dv, int G, double reg, int raw, hipStream_t s) {

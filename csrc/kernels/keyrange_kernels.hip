@@ -4,6 +4,7 @@
 #include <hip/hip_runtime.h>
 
 #include "common.h"
+#include "dispatch.h"
 #include "keyrange_kernels.h"
 #include "wide_kernels.h"
 
@@ -181,13 +182,10 @@ void launch_kr_worker_rows(int K, int KP, const int64_t* indptr, const int32_t* 
   if (T <= 0) return;
   const int grid = kr_grid((int64_t)T * 16);
   char* sl = static_cast<char*>(slot);
-  switch (KP) {
-    case 1: kr_worker_rows_kernel<1><<<grid, 256, 0, s>>>(K, indptr, idx, val, y, T, z, htab, hmask, dloc, wloc_b, dz, acc, ticket, sl, loss, seq); break;
-    case 2: kr_worker_rows_kernel<2><<<grid, 256, 0, s>>>(K, indptr, idx, val, y, T, z, htab, hmask, dloc, wloc_b, dz, acc, ticket, sl, loss, seq); break;
-    case 4: kr_worker_rows_kernel<4><<<grid, 256, 0, s>>>(K, indptr, idx, val, y, T, z, htab, hmask, dloc, wloc_b, dz, acc, ticket, sl, loss, seq); break;
-    case 8: kr_worker_rows_kernel<8><<<grid, 256, 0, s>>>(K, indptr, idx, val, y, T, z, htab, hmask, dloc, wloc_b, dz, acc, ticket, sl, loss, seq); break;
-    default: kr_worker_rows_kernel<16><<<grid, 256, 0, s>>>(K, indptr, idx, val, y, T, z, htab, hmask, dloc, wloc_b, dz, acc, ticket, sl, loss, seq); break;
-  }
+  dispatch_wide_kp("key-range worker rows: padded classes", KP, [&](auto kp) {
+    kr_worker_rows_kernel<kp()><<<grid, 256, 0, s>>>(K, indptr, idx, val, y, T, z, htab, hmask, dloc, wloc_b, dz, acc,
+                                                     ticket, sl, loss, seq);
+  });
 }
 
 void launch_kr_server_rows(int K, int KP, const int32_t* y, int T, float* z, const float* dz, float lr, const float* b,
@@ -195,13 +193,9 @@ void launch_kr_server_rows(int K, int KP, const int32_t* y, int T, float* z, con
   if (T <= 0) return;
   const int grid = kr_grid(T) < 256 ? kr_grid(T) : 256;
   char* sl = static_cast<char*>(slot);
-  switch (KP) {
-    case 1: kr_server_rows_kernel<1><<<grid, 256, 0, s>>>(K, y, T, z, dz, lr, b, acc, ticket, sl, seq); break;
-    case 2: kr_server_rows_kernel<2><<<grid, 256, 0, s>>>(K, y, T, z, dz, lr, b, acc, ticket, sl, seq); break;
-    case 4: kr_server_rows_kernel<4><<<grid, 256, 0, s>>>(K, y, T, z, dz, lr, b, acc, ticket, sl, seq); break;
-    case 8: kr_server_rows_kernel<8><<<grid, 256, 0, s>>>(K, y, T, z, dz, lr, b, acc, ticket, sl, seq); break;
-    default: kr_server_rows_kernel<16><<<grid, 256, 0, s>>>(K, y, T, z, dz, lr, b, acc, ticket, sl, seq); break;
-  }
+  dispatch_wide_kp("key-range server rows: padded classes", KP, [&](auto kp) {
+    kr_server_rows_kernel<kp()><<<grid, 256, 0, s>>>(K, y, T, z, dz, lr, b, acc, ticket, sl, seq);
+  });
 }
 
 void launch_kr_gather(const float* shard, int64_t lo, int KP, const int32_t* ids, const unsigned* n_dev, int n_host,

@@ -11,6 +11,7 @@
 // 63-98 (pull -> train on the buffer -> log -> push), MessageTracker.java:69-87.
 #include <cstdlib>
 
+#include "dispatch.h"
 #include "lanes_body.h"
 #include "lanes_kernels.h"
 #include "solve_body.h"
@@ -547,17 +548,6 @@ void launch_afk(const SolverCfg& cfg, const AsyncPack& pk, const AsyncLaneDev* a
     launch_afks<FP, KP, 1, false>(pk, al, s);
 }
 
-template <int FP>
-void launch_af(const SolverCfg& cfg, const AsyncPack& pk, const AsyncLaneDev* al, int S, hipStream_t s) {
-  const int KP = padded_classes(cfg.K);
-  if (KP <= 2)
-    launch_afk<FP, 2>(cfg, pk, al, S, s);
-  else if (KP <= 4)
-    launch_afk<FP, 4>(cfg, pk, al, S, s);
-  else
-    launch_afk<FP, 8>(cfg, pk, al, S, s);
-}
-
 }  // namespace
 
 void launch_async_init(const SolverCfg& cfg, const AsyncArgs& a, unsigned long long t, hipStream_t s) {
@@ -566,13 +556,11 @@ void launch_async_init(const SolverCfg& cfg, const AsyncArgs& a, unsigned long l
 }
 
 void launch_lanes_async(const SolverCfg& cfg, const AsyncPack& pk, const AsyncLaneDev* al, int S, hipStream_t s) {
-  switch (cfg.Fp) {
-    case 128: launch_af<128>(cfg, pk, al, S, s); break;
-    case 256: launch_af<256>(cfg, pk, al, S, s); break;
-    case 512: launch_af<512>(cfg, pk, al, S, s); break;
-    case 1024: launch_af<1024>(cfg, pk, al, S, s); break;
-    default: break;
-  }
+  dispatch_int<128, 256, 512, 1024>("async lanes: padded width", cfg.Fp, [&](auto fp) {
+    dispatch_int<2, 4, 8>("async lanes: padded classes", padded_classes(cfg.K), [&](auto kp) {
+      launch_afk<fp(), kp()>(cfg, pk, al, S, s);
+    });
+  });
 }
 
 }  // namespace psx

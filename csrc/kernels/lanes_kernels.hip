@@ -3,6 +3,7 @@
 
 #include <cstdlib>
 
+#include "dispatch.h"
 #include "lanes_body.h"
 #include "solve_body.h"
 
@@ -362,27 +363,14 @@ void launch_fk(const SolverCfg& cfg, const LaneDev* lanes, const LanesArgs& a, i
     launch_fks<FP, KP, 1, false>(cfg, lanes, a, s);
 }
 
-template <int FP>
-void launch_f(const SolverCfg& cfg, const LaneDev* lanes, const LanesArgs& a, int S, hipStream_t s) {
-  const int KP = padded_classes(cfg.K);
-  if (KP <= 2)
-    launch_fk<FP, 2>(cfg, lanes, a, S, s);
-  else if (KP <= 4)
-    launch_fk<FP, 4>(cfg, lanes, a, S, s);
-  else
-    launch_fk<FP, 8>(cfg, lanes, a, S, s);
-}
-
 }  // namespace
 
 void launch_lanes_round(const SolverCfg& cfg, const LaneDev* lanes_dev, const LanesArgs& a, int S, hipStream_t s) {
-  switch (cfg.Fp) {
-    case 128: launch_f<128>(cfg, lanes_dev, a, S, s); break;
-    case 256: launch_f<256>(cfg, lanes_dev, a, S, s); break;
-    case 512: launch_f<512>(cfg, lanes_dev, a, S, s); break;
-    case 1024: launch_f<1024>(cfg, lanes_dev, a, S, s); break;
-    default: break;
-  }
+  dispatch_int<128, 256, 512, 1024>("lanes round: padded width", cfg.Fp, [&](auto fp) {
+    dispatch_int<2, 4, 8>("lanes round: padded classes", padded_classes(cfg.K), [&](auto kp) {
+      launch_fk<fp(), kp()>(cfg, lanes_dev, a, S, s);
+    });
+  });
 }
 
 void launch_xcc_probe(int* ids, int n, hipStream_t s) { xcc_probe_kernel<<<n, 64, 0, s>>>(ids, n); }
@@ -595,13 +583,9 @@ int lanes_eval_grid() {  // PSX_SIDE_GRID: workgroups of the evaluation launch (
 void launch_lanes_eval(const SolverCfg& cfg, const EvalMulti& ev, hipStream_t s) {
   if (ev.nmodels <= 0) return;
   const int g = lanes_eval_grid();
-  switch (cfg.Fp) {
-    case 128: lanes_eval_kernel<128><<<g, 256, 0, s>>>(ev); break;
-    case 256: lanes_eval_kernel<256><<<g, 256, 0, s>>>(ev); break;
-    case 512: lanes_eval_kernel<512><<<g, 256, 0, s>>>(ev); break;
-    case 1024: lanes_eval_kernel<1024><<<g, 256, 0, s>>>(ev); break;
-    default: break;
-  }
+  dispatch_int<128, 256, 512, 1024>("lanes eval: padded width", cfg.Fp, [&](auto fp) {
+    lanes_eval_kernel<fp()><<<g, 256, 0, s>>>(ev);
+  });
 }
 
 }  // namespace psx

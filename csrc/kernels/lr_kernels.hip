@@ -15,6 +15,7 @@
 //              the B-operand fragment order of v_mfma_f32_16x16x32_bf16.
 #include <hip/hip_runtime.h>
 
+#include "dispatch.h"
 #include "eval_body.h"
 #include "lr_kernels.h"
 #include "solve_kernels.h"
@@ -115,20 +116,7 @@ void launch_eval_apply(int FP, int K, const uint16_t* Xt, const int32_t* yt, int
   r.slot2 = static_cast<char*>(slot2);
   r.seq2 = seq2;
   r.nticket = (unsigned)grid;
-#define PSX_TE(FPV)                                             \
-  case FPV:                                                     \
-    test_eval_kernel<FPV><<<grid, 256, lds, s>>>(r, a);         \
-    break;
-  switch (FP) {
-    PSX_TE(128)
-    PSX_TE(256)
-    PSX_TE(512)
-    PSX_TE(1024)
-    PSX_TE(2048)
-    default:
-      break;
-  }
-#undef PSX_TE
+  dispatch_fp("test_eval: padded width", FP, [&](auto fp) { test_eval_kernel<fp()><<<grid, 256, lds, s>>>(r, a); });
 }
 
 // Logits for T rows (tests / debugging): logits[T][K].
@@ -163,20 +151,9 @@ void launch_logits(int FP, int K, const uint16_t* X, int T, const uint16_t* wf_h
   const int ntiles = (T + 31) / 32;
   const int grid = ntiles < 1024 ? ntiles : 1024;
   if (grid <= 0) return;
-#define PSX_LG(FPV)                                                                  \
-  case FPV:                                                                          \
-    logits_kernel<FPV><<<grid, 256, lds, s>>>(K, X, T, wf_hi, wf_lo, b, logits); \
-    break;
-  switch (FP) {
-    PSX_LG(128)
-    PSX_LG(256)
-    PSX_LG(512)
-    PSX_LG(1024)
-    PSX_LG(2048)
-    default:
-      break;
-  }
-#undef PSX_LG
+  dispatch_fp("logits: padded width", FP, [&](auto fp) {
+    logits_kernel<fp()><<<grid, 256, lds, s>>>(K, X, T, wf_hi, wf_lo, b, logits);
+  });
 }
 
 // ---------------------------------------------------------------------------
@@ -285,21 +262,14 @@ void launch_ring_ingest(const uint16_t* src, const int32_t* ysrc, int64_t src_fi
 // ---------------------------------------------------------------------------
 // Allow the wide tiles to use more than the default 64 KiB of dynamic LDS
 // (gfx950: 160 KiB per CU).  Must run before any launch / graph capture.
-template <int FP>
-static void set_lds_attr() {
-  const int bytes = (int)eval_lds_bytes(FP);
-  (void)hipFuncSetAttribute((const void*)test_eval_kernel<FP>, hipFuncAttributeMaxDynamicSharedMemorySize, bytes);
-  (void)hipFuncSetAttribute((const void*)logits_kernel<FP>, hipFuncAttributeMaxDynamicSharedMemorySize, bytes);
-}
-
 void prepare_kernels() {
   static bool done = false;
   if (done) return;
-  set_lds_attr<128>();
-  set_lds_attr<256>();
-  set_lds_attr<512>();
-  set_lds_attr<1024>();
-  set_lds_attr<2048>();
+  for_each_fp([](auto fp) {
+    const int bytes = (int)eval_lds_bytes(fp());
+    (void)hipFuncSetAttribute((const void*)test_eval_kernel<fp()>, hipFuncAttributeMaxDynamicSharedMemorySize, bytes);
+    (void)hipFuncSetAttribute((const void*)logits_kernel<fp()>, hipFuncAttributeMaxDynamicSharedMemorySize, bytes);
+  });
   prepare_solve_kernels();
   done = true;
 }

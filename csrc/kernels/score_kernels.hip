@@ -5,6 +5,7 @@
 // row's prediction, probabilities and loss reach the caller, in one pass.
 #include <hip/hip_runtime.h>
 
+#include "dispatch.h"
 #include "lr_kernels.h"
 #include "score_kernels.h"
 #include "tile.h"
@@ -263,37 +264,20 @@ __global__ __launch_bounds__(256) void wide_score_kernel(int K, int64_t F, const
 }
 
 // ---------------------------------------------------------------------------
-template <int FP>
-static void set_score_lds_attr() {
-  (void)hipFuncSetAttribute((const void*)score_kernel<FP>, hipFuncAttributeMaxDynamicSharedMemorySize,
-                            (int)eval_lds_bytes(FP));
-  (void)hipFuncSetAttribute((const void*)score_kernel<FP, kHistGlobal>, hipFuncAttributeMaxDynamicSharedMemorySize,
-                            (int)eval_lds_bytes(FP));
-  const size_t room = kLdsPerWorkgroup - eval_lds_bytes(FP);
-  const size_t table = room < 16 * kHistCells * 4 ? room / (kHistCells * 4) * (kHistCells * 4) : 16 * kHistCells * 4;
-  (void)hipFuncSetAttribute((const void*)score_kernel<FP, kHistLds>, hipFuncAttributeMaxDynamicSharedMemorySize,
-                            (int)(eval_lds_bytes(FP) + table));
-}
-
-template <int KP>
-static void set_wide_hist_lds_attr() {  // 64 KB of table at K = 16, beside 1 KB of static LDS
-  (void)hipFuncSetAttribute((const void*)wide_score_kernel<KP, true>, hipFuncAttributeMaxDynamicSharedMemorySize,
-                            KP * kHistCells * 4);
-}
-
 void prepare_score_kernels() {
   static bool done = false;
   if (done) return;
-  set_score_lds_attr<128>();
-  set_score_lds_attr<256>();
-  set_score_lds_attr<512>();
-  set_score_lds_attr<1024>();
-  set_score_lds_attr<2048>();
-  set_wide_hist_lds_attr<1>();
-  set_wide_hist_lds_attr<2>();
-  set_wide_hist_lds_attr<4>();
-  set_wide_hist_lds_attr<8>();
-  set_wide_hist_lds_attr<16>();
+  constexpr hipFuncAttribute kDyn = hipFuncAttributeMaxDynamicSharedMemorySize;
+  for_each_fp([&](auto fp) {
+    const size_t tile = eval_lds_bytes(fp()), room = kLdsPerWorkgroup - tile;
+    const size_t table = room < 16 * kHistCells * 4 ? room / (kHistCells * 4) * (kHistCells * 4) : 16 * kHistCells * 4;
+    (void)hipFuncSetAttribute((const void*)score_kernel<fp()>, kDyn, (int)tile);
+    (void)hipFuncSetAttribute((const void*)score_kernel<fp(), kHistGlobal>, kDyn, (int)tile);
+    (void)hipFuncSetAttribute((const void*)score_kernel<fp(), kHistLds>, kDyn, (int)(tile + table));
+  });
+  for_each_wide_kp([&](auto kp) {  // 64 KB of table at K = 16, beside 1 KB of static LDS
+    (void)hipFuncSetAttribute((const void*)wide_score_kernel<kp(), true>, kDyn, kp() * kHistCells * 4);
+  });
   done = true;
 }
 
@@ -312,25 +296,14 @@ bool launch_score(int FP, int K, const uint16_t* X, const int32_t* y, int T, con
   const int ntiles = (T + 31) / 32;
   const int grid = ntiles < 1024 ? ntiles : 1024;
   if (grid <= 0) return true;
-#define PSX_SC(FPV)                                                                             \
-  case FPV:                                                                                     \
-    if (hm == kHistLds)                                                                         \
-      score_kernel<FPV, kHistLds><<<grid, 256, lds, s>>>(K, X, y, T, wf_hi, wf_lo, b, o);    \
-    else if (hm == kHistGlobal)                                                                 \
-      score_kernel<FPV, kHistGlobal><<<grid, 256, lds, s>>>(K, X, y, T, wf_hi, wf_lo, b, o); \
-    else                                                                                        \
-      score_kernel<FPV><<<grid, 256, lds, s>>>(K, X, y, T, wf_hi, wf_lo, b, o);              \
-    break;
-  switch (FP) {
-    PSX_SC(128)
-    PSX_SC(256)
-    PSX_SC(512)
-    PSX_SC(1024)
-    PSX_SC(2048)
-    default:
-      break;
-  }
-#undef PSX_SC
+  dispatch_fp("score: padded width", FP, [&](auto fp) {
+    if (hm == kHistLds)
+      score_kernel<fp(), kHistLds><<<grid, 256, lds, s>>>(K, X, y, T, wf_hi, wf_lo, b, o);
+    else if (hm == kHistGlobal)
+      score_kernel<fp(), kHistGlobal><<<grid, 256, lds, s>>>(K, X, y, T, wf_hi, wf_lo, b, o);
+    else
+      score_kernel<fp()><<<grid, 256, lds, s>>>(K, X, y, T, wf_hi, wf_lo, b, o);
+  });
   return true;
 }
 
@@ -340,23 +313,12 @@ void launch_wide_score(int K, int KP, int64_t F, const int64_t* indptr, const in
   const int nwg = (T + 3) / 4;  // 4 rows per workgroup pass
   const int grid = nwg < 1024 ? nwg : 1024;
   const bool hist = o.hist != nullptr && y != nullptr;
-#define PSX_WS(KV)                                                                                                  \
-  case KV:                                                                                                          \
-    if (hist)                                                                                                       \
-      wide_score_kernel<KV, true><<<grid, 256, K * kHistCells * 4, s>>>(K, F, indptr, idx, val, y, T, w, o);     \
-    else                                                                                                            \
-      wide_score_kernel<KV><<<grid, 256, 0, s>>>(K, F, indptr, idx, val, y, T, w, o);                            \
-    break;
-  switch (KP) {
-    PSX_WS(1)
-    PSX_WS(2)
-    PSX_WS(4)
-    PSX_WS(8)
-    PSX_WS(16)
-    default:
-      break;
-  }
-#undef PSX_WS
+  dispatch_wide_kp("wide_score: padded classes", KP, [&](auto kp) {
+    if (hist)
+      wide_score_kernel<kp(), true><<<grid, 256, K * kHistCells * 4, s>>>(K, F, indptr, idx, val, y, T, w, o);
+    else
+      wide_score_kernel<kp()><<<grid, 256, 0, s>>>(K, F, indptr, idx, val, y, T, w, o);
+  });
 }
 
 }  // namespace psx

@@ -1,4 +1,5 @@
 // Persistent server kernel of the peer data plane (see server_persist.h).
+#include "dispatch.h"
 #include "lanes_body.h"
 #include "server_persist.h"
 #include "solve_body.h"
@@ -442,13 +443,9 @@ size_t server_persist_lds_bytes() { return (size_t)kPairEvalLds; }
 void launch_server_persist(const SrvArgs& a, int FP, hipStream_t s) {
   const size_t lds = server_persist_lds_bytes();
   if (a.nwg < 1 || a.nwg > kSrvWg) return;
-  switch (FP) {
-    case 128: server_persist_kernel<128><<<8 * a.nwg, 256, lds, s>>>(a); break;
-    case 256: server_persist_kernel<256><<<8 * a.nwg, 256, lds, s>>>(a); break;
-    case 512: server_persist_kernel<512><<<8 * a.nwg, 256, lds, s>>>(a); break;
-    case 1024: server_persist_kernel<1024><<<8 * a.nwg, 256, lds, s>>>(a); break;
-    default: break;
-  }
+  dispatch_int<128, 256, 512, 1024>("persistent server: padded width", FP, [&](auto fp) {
+    server_persist_kernel<fp()><<<8 * a.nwg, 256, lds, s>>>(a);
+  });
 }
 
 }  // namespace psx

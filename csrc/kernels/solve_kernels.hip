@@ -38,6 +38,7 @@
 
 #include <cstdlib>
 
+#include "dispatch.h"
 #include "eval_body.h"
 #include "lr_kernels.h"
 #include "solve_kernels.h"
@@ -45,6 +46,10 @@
 #include "solve_body.h"
 
 namespace psx {
+
+static const char kSolveFP[] = "solve: padded width", kSolveKP[] = "solve: padded classes",
+                  kSolveFP32[] = "solve: padded width of fp32 rows", kPersistFP[] = "persistent solve: padded width",
+                  kPersistKP[] = "persistent solve: padded classes";
 
 int xch_words() { return kXchFlags + 32 * kMaxXcdWg; }
 // ---------------------------------------------------------------------------
@@ -363,12 +368,9 @@ __global__ __launch_bounds__(256) void finalize_kernel(SolverCfg cfg, const Ctrl
 
 void launch_finalize(const SolverCfg& cfg, const Ctrl* ctrl, const SolveDev& dv, hipStream_t s) {
   const int grid = (cfg.Fp + 255) / 256;
-  switch (dv.KP) {
-    case 2: finalize_kernel<2><<<grid, 256, 0, s>>>(cfg, ctrl, dv); break;
-    case 4: finalize_kernel<4><<<grid, 256, 0, s>>>(cfg, ctrl, dv); break;
-    case 8: finalize_kernel<8><<<grid, 256, 0, s>>>(cfg, ctrl, dv); break;
-    default: finalize_kernel<16><<<grid, 256, 0, s>>>(cfg, ctrl, dv); break;
-  }
+  dispatch_int<2, 4, 8, 16>(kSolveKP, dv.KP, [&](auto kp) {
+    finalize_kernel<kp()><<<grid, 256, 0, s>>>(cfg, ctrl, dv);
+  });
 }
 
 template <int FP, int KP>
@@ -455,20 +457,10 @@ static void launch_bwd_fp(const SolverCfg& cfg, const SolveParams* prm, Ctrl* ct
                           int ride_t0 = 0, int nride = 0, int fin_slot = kNoFinSlot) {
   const int ns = bwd_grid(FP), ng = xcd_grid(ns, nride, bwd_scope<FP>() == 2 && cfg.xcd >= 0, cfg.xcd & 7);
   const size_t bl = nride > 0 ? bwd_ride_lds_bytes(FP) : bwd_lds_bytes();
-  switch (dv.KP) {
-    case 2:
-      bwd_update_kernel<FP, 2><<<ng, 256, bl, s>>>(cfg, prm, ctrl, slot, dv, nwg, win, ns, ride, ride_t0, nride, fin_slot);
-      break;
-    case 4:
-      bwd_update_kernel<FP, 4><<<ng, 256, bl, s>>>(cfg, prm, ctrl, slot, dv, nwg, win, ns, ride, ride_t0, nride, fin_slot);
-      break;
-    case 8:
-      bwd_update_kernel<FP, 8><<<ng, 256, bl, s>>>(cfg, prm, ctrl, slot, dv, nwg, win, ns, ride, ride_t0, nride, fin_slot);
-      break;
-    default:
-      bwd_update_kernel<FP, 16><<<ng, 256, bl, s>>>(cfg, prm, ctrl, slot, dv, nwg, win, ns, ride, ride_t0, nride, fin_slot);
-      break;
-  }
+  dispatch_int<2, 4, 8, 16>(kSolveKP, dv.KP, [&](auto kp) {
+    bwd_update_kernel<FP, kp()><<<ng, 256, bl, s>>>(cfg, prm, ctrl, slot, dv, nwg, win, ns, ride, ride_t0, nride,
+                                                    fin_slot);
+  });
 }
 
 template <int FP>
@@ -481,39 +473,22 @@ static void launch_slot_fp(const SolverCfg& cfg, const SolveParams* prm, Ctrl* c
 
 void launch_bwd(const SolverCfg& cfg, const SolveParams* prm, Ctrl* ctrl, int slot, const SolveDev& dv, int fwd_grid,
                 hipStream_t s, const SolveParams& win) {
-  switch (cfg.Fp) {
-    case 128: launch_bwd_fp<128>(cfg, prm, ctrl, slot, dv, fwd_grid, s, win); break;
-    case 256: launch_bwd_fp<256>(cfg, prm, ctrl, slot, dv, fwd_grid, s, win); break;
-    case 512: launch_bwd_fp<512>(cfg, prm, ctrl, slot, dv, fwd_grid, s, win); break;
-    case 1024: launch_bwd_fp<1024>(cfg, prm, ctrl, slot, dv, fwd_grid, s, win); break;
-    case 2048: launch_bwd_fp<2048>(cfg, prm, ctrl, slot, dv, fwd_grid, s, win); break;
-    default: break;
-  }
+  dispatch_fp(kSolveFP, cfg.Fp, [&](auto fp) { launch_bwd_fp<fp()>(cfg, prm, ctrl, slot, dv, fwd_grid, s, win); });
 }
 
 void launch_slot_ride(const SolverCfg& cfg, const SolveParams* prm, Ctrl* ctrl, int slot, const SolveDev& dv, int nwg,
                       hipStream_t s, const SolveParams& win, const EvalRide& ride, int ride_t0, int nride,
                       int fin_slot) {
-  switch (cfg.Fp) {
-    case 128: launch_slot_fp<128>(cfg, prm, ctrl, slot, dv, nwg, s, win, fin_slot, ride, ride_t0, nride); break;
-    case 256: launch_slot_fp<256>(cfg, prm, ctrl, slot, dv, nwg, s, win, fin_slot, ride, ride_t0, nride); break;
-    case 512: launch_slot_fp<512>(cfg, prm, ctrl, slot, dv, nwg, s, win, fin_slot, ride, ride_t0, nride); break;
-    case 1024: launch_slot_fp<1024>(cfg, prm, ctrl, slot, dv, nwg, s, win, fin_slot, ride, ride_t0, nride); break;
-    case 2048: launch_slot_fp<2048>(cfg, prm, ctrl, slot, dv, nwg, s, win, fin_slot, ride, ride_t0, nride); break;
-    default: break;
-  }
+  dispatch_fp(kSolveFP, cfg.Fp, [&](auto fp) {
+    launch_slot_fp<fp()>(cfg, prm, ctrl, slot, dv, nwg, s, win, fin_slot, ride, ride_t0, nride);
+  });
 }
 
 void launch_slot(const SolverCfg& cfg, const SolveParams* prm, Ctrl* ctrl, int slot, const SolveDev& dv, int nwg,
                  hipStream_t s, const SolveParams& win, int fin_slot) {
-  switch (cfg.Fp) {
-    case 128: launch_slot_fp<128>(cfg, prm, ctrl, slot, dv, nwg, s, win, fin_slot); break;
-    case 256: launch_slot_fp<256>(cfg, prm, ctrl, slot, dv, nwg, s, win, fin_slot); break;
-    case 512: launch_slot_fp<512>(cfg, prm, ctrl, slot, dv, nwg, s, win, fin_slot); break;
-    case 1024: launch_slot_fp<1024>(cfg, prm, ctrl, slot, dv, nwg, s, win, fin_slot); break;
-    case 2048: launch_slot_fp<2048>(cfg, prm, ctrl, slot, dv, nwg, s, win, fin_slot); break;
-    default: break;
-  }
+  dispatch_fp(kSolveFP, cfg.Fp, [&](auto fp) {
+    launch_slot_fp<fp()>(cfg, prm, ctrl, slot, dv, nwg, s, win, fin_slot);
+  });
 }
 
 size_t tail_lds_bytes(int FP) {
@@ -532,24 +507,16 @@ static void launch_tail_fp(const SolverCfg& cfg, const SolveParams* prm, Ctrl* c
   const size_t lb = tail_lds_bytes(FP);
   const int flag = (int)(lb - 16);
   const int nfin = fin ? cfg.Fp / 32 : 0;  // 32-feature slices; <= G: G >= FP/32 workgroups
-  switch (dv.KP) {
-    case 2: tail_kernel<FP, 2><<<G, 256, lb, s>>>(cfg, prm, ctrl, s0, s1, dv, ns, flag, nfin); break;
-    case 4: tail_kernel<FP, 4><<<G, 256, lb, s>>>(cfg, prm, ctrl, s0, s1, dv, ns, flag, nfin); break;
-    case 8: tail_kernel<FP, 8><<<G, 256, lb, s>>>(cfg, prm, ctrl, s0, s1, dv, ns, flag, nfin); break;
-    default: tail_kernel<FP, 16><<<G, 256, lb, s>>>(cfg, prm, ctrl, s0, s1, dv, ns, flag, nfin); break;
-  }
+  dispatch_int<2, 4, 8, 16>(kSolveKP, dv.KP, [&](auto kp) {
+    tail_kernel<FP, kp()><<<G, 256, lb, s>>>(cfg, prm, ctrl, s0, s1, dv, ns, flag, nfin);
+  });
 }
 
 void launch_tail(const SolverCfg& cfg, const SolveParams* prm, Ctrl* ctrl, int slot_begin, int slot_end,
                  const SolveDev& dv, int nwg, hipStream_t s, int with_finalize) {
-  switch (cfg.Fp) {
-    case 128: launch_tail_fp<128>(cfg, prm, ctrl, slot_begin, slot_end, dv, nwg, with_finalize, s); break;
-    case 256: launch_tail_fp<256>(cfg, prm, ctrl, slot_begin, slot_end, dv, nwg, with_finalize, s); break;
-    case 512: launch_tail_fp<512>(cfg, prm, ctrl, slot_begin, slot_end, dv, nwg, with_finalize, s); break;
-    case 1024: launch_tail_fp<1024>(cfg, prm, ctrl, slot_begin, slot_end, dv, nwg, with_finalize, s); break;
-    case 2048: launch_tail_fp<2048>(cfg, prm, ctrl, slot_begin, slot_end, dv, nwg, with_finalize, s); break;
-    default: break;
-  }
+  dispatch_fp(kSolveFP, cfg.Fp, [&](auto fp) {
+    launch_tail_fp<fp()>(cfg, prm, ctrl, slot_begin, slot_end, dv, nwg, with_finalize, s);
+  });
 }
 
 // ---------------------------------------------------------------------------
@@ -775,24 +742,12 @@ void launch_ring_ingest_f32(const float* src, const int32_t* ysrc, int64_t src_f
 void launch_stats_rows(const SolverCfg& cfg, SolveParams* prm, const SolveDev& dv, int B, int start, int G,
                        hipStream_t s) {
   const size_t lb = stats_rows_lds_bytes();
-  if (cfg.xf32) {
-    switch (cfg.Fp) {
-      case 128: stats_rows_kernel<128, true><<<G, 256, lb, s>>>(cfg, prm, dv, B, start); break;
-      case 256: stats_rows_kernel<256, true><<<G, 256, lb, s>>>(cfg, prm, dv, B, start); break;
-      case 512: stats_rows_kernel<512, true><<<G, 256, lb, s>>>(cfg, prm, dv, B, start); break;
-      case 1024: stats_rows_kernel<1024, true><<<G, 256, lb, s>>>(cfg, prm, dv, B, start); break;
-      default: break;
-    }
-    return;
-  }
-  switch (cfg.Fp) {
-    case 128: stats_rows_kernel<128><<<G, 256, lb, s>>>(cfg, prm, dv, B, start); break;
-    case 256: stats_rows_kernel<256><<<G, 256, lb, s>>>(cfg, prm, dv, B, start); break;
-    case 512: stats_rows_kernel<512><<<G, 256, lb, s>>>(cfg, prm, dv, B, start); break;
-    case 1024: stats_rows_kernel<1024><<<G, 256, lb, s>>>(cfg, prm, dv, B, start); break;
-    case 2048: stats_rows_kernel<2048><<<G, 256, lb, s>>>(cfg, prm, dv, B, start); break;
-    default: break;
-  }
+  if (cfg.xf32)
+    dispatch_int<128, 256, 512, 1024>(kSolveFP32, cfg.Fp, [&](auto fp) {
+      stats_rows_kernel<fp(), true><<<G, 256, lb, s>>>(cfg, prm, dv, B, start);
+    });
+  else
+    dispatch_fp(kSolveFP, cfg.Fp, [&](auto fp) { stats_rows_kernel<fp()><<<G, 256, lb, s>>>(cfg, prm, dv, B, start); });
 }
 
 void launch_prep_rows(const SolverCfg& cfg, const SolveParams* prm, const SolveDev& dv, Ctrl* ctrl, int G,
@@ -805,26 +760,15 @@ size_t fwdbwd_rows_lds_bytes(int FP, bool f32) { return fwd_lds_bytes(FP) + (f32
 
 void launch_fwdbwd_rows(const SolverCfg& cfg, const SolveParams* prm, const Ctrl* ctrl, int slot, const SolveDev& dv,
                         int G, hipStream_t s) {
-  if (cfg.xf32) {
-    const size_t lb = fwdbwd_rows_lds_bytes(cfg.Fp, true);
-    switch (cfg.Fp) {
-      case 128: fwdbwd_rows_kernel<128, true><<<G, 256, lb, s>>>(cfg, prm, ctrl, slot, dv); break;
-      case 256: fwdbwd_rows_kernel<256, true><<<G, 256, lb, s>>>(cfg, prm, ctrl, slot, dv); break;
-      case 512: fwdbwd_rows_kernel<512, true><<<G, 256, lb, s>>>(cfg, prm, ctrl, slot, dv); break;
-      case 1024: fwdbwd_rows_kernel<1024, true><<<G, 256, lb, s>>>(cfg, prm, ctrl, slot, dv); break;
-      default: break;
-    }
-    return;
-  }
-  const size_t lb = fwd_lds_bytes(cfg.Fp);
-  switch (cfg.Fp) {
-    case 128: fwdbwd_rows_kernel<128><<<G, 256, lb, s>>>(cfg, prm, ctrl, slot, dv); break;
-    case 256: fwdbwd_rows_kernel<256><<<G, 256, lb, s>>>(cfg, prm, ctrl, slot, dv); break;
-    case 512: fwdbwd_rows_kernel<512><<<G, 256, lb, s>>>(cfg, prm, ctrl, slot, dv); break;
-    case 1024: fwdbwd_rows_kernel<1024><<<G, 256, lb, s>>>(cfg, prm, ctrl, slot, dv); break;
-    case 2048: fwdbwd_rows_kernel<2048><<<G, 256, lb, s>>>(cfg, prm, ctrl, slot, dv); break;
-    default: break;
-  }
+  const size_t lb = fwdbwd_rows_lds_bytes(cfg.Fp, cfg.xf32);
+  if (cfg.xf32)
+    dispatch_int<128, 256, 512, 1024>(kSolveFP32, cfg.Fp, [&](auto fp) {
+      fwdbwd_rows_kernel<fp(), true><<<G, 256, lb, s>>>(cfg, prm, ctrl, slot, dv);
+    });
+  else
+    dispatch_fp(kSolveFP, cfg.Fp, [&](auto fp) {
+      fwdbwd_rows_kernel<fp()><<<G, 256, lb, s>>>(cfg, prm, ctrl, slot, dv);
+    });
 }
 
 void launch_reduce_g(const SolverCfg& cfg, const SolveParams* prm, const Ctrl* ctrl, const SolveDev& dv, int G,
@@ -972,11 +916,9 @@ static void launch_persist_fps(const SolverCfg& cfg, const SolveDev& dv, Ctrl* c
                                const EvalRide& ride, int nride, hipStream_t s) {
   const size_t lb = persist_lds_bytes(FP);
   const int grid = xcd_grid(G, nride, S == 2, cfg.xcd & 7);
-  switch (dv.KP) {
-    case 2: solve_persist_kernel<FP, 2, S><<<grid, 256, lb, s>>>(cfg, dv, ctrl, win, G, ride, nride); break;
-    case 4: solve_persist_kernel<FP, 4, S><<<grid, 256, lb, s>>>(cfg, dv, ctrl, win, G, ride, nride); break;
-    default: solve_persist_kernel<FP, 8, S><<<grid, 256, lb, s>>>(cfg, dv, ctrl, win, G, ride, nride); break;
-  }
+  dispatch_int<2, 4, 8>(kPersistKP, dv.KP, [&](auto kp) {
+    solve_persist_kernel<FP, kp(), S><<<grid, 256, lb, s>>>(cfg, dv, ctrl, win, G, ride, nride);
+  });
 }
 
 template <int FP>
@@ -997,59 +939,32 @@ bool persist_supported(int FP, int KP) { return FP >= 128 && FP <= 1024 && KP <=
 
 void launch_persist(const SolverCfg& cfg, const SolveDev& dv, Ctrl* ctrl, const SolveParams& win, int G,
                     const EvalRide& ride, int nride, hipStream_t s) {
-  switch (cfg.Fp) {
-    case 128: launch_persist_fp<128>(cfg, dv, ctrl, win, G, ride, nride, s); break;
-    case 256: launch_persist_fp<256>(cfg, dv, ctrl, win, G, ride, nride, s); break;
-    case 512: launch_persist_fp<512>(cfg, dv, ctrl, win, G, ride, nride, s); break;
-    case 1024: launch_persist_fp<1024>(cfg, dv, ctrl, win, G, ride, nride, s); break;
-    default: break;
-  }
+  dispatch_int<128, 256, 512, 1024>(kPersistFP, cfg.Fp, [&](auto fp) {
+    launch_persist_fp<fp()>(cfg, dv, ctrl, win, G, ride, nride, s);
+  });
 }
 
-template <int FP>
-static void set_persist_attr() {
-  const int b = (int)persist_lds_bytes(FP);
-  (void)hipFuncSetAttribute((const void*)solve_persist_kernel<FP, 2, 1>, hipFuncAttributeMaxDynamicSharedMemorySize, b);
-  (void)hipFuncSetAttribute((const void*)solve_persist_kernel<FP, 4, 1>, hipFuncAttributeMaxDynamicSharedMemorySize, b);
-  (void)hipFuncSetAttribute((const void*)solve_persist_kernel<FP, 8, 1>, hipFuncAttributeMaxDynamicSharedMemorySize, b);
-  (void)hipFuncSetAttribute((const void*)solve_persist_kernel<FP, 2, 2>, hipFuncAttributeMaxDynamicSharedMemorySize, b);
-  (void)hipFuncSetAttribute((const void*)solve_persist_kernel<FP, 4, 2>, hipFuncAttributeMaxDynamicSharedMemorySize, b);
-  (void)hipFuncSetAttribute((const void*)solve_persist_kernel<FP, 8, 2>, hipFuncAttributeMaxDynamicSharedMemorySize, b);
-}
-
-template <int FP>
-static void set_slot_attr() {
-  const int tb = (int)tail_lds_bytes(FP);
-  (void)hipFuncSetAttribute((const void*)tail_kernel<FP, 2>, hipFuncAttributeMaxDynamicSharedMemorySize, tb);
-  (void)hipFuncSetAttribute((const void*)tail_kernel<FP, 4>, hipFuncAttributeMaxDynamicSharedMemorySize, tb);
-  (void)hipFuncSetAttribute((const void*)tail_kernel<FP, 8>, hipFuncAttributeMaxDynamicSharedMemorySize, tb);
-  (void)hipFuncSetAttribute((const void*)tail_kernel<FP, 16>, hipFuncAttributeMaxDynamicSharedMemorySize, tb);
-  (void)hipFuncSetAttribute((const void*)fwd_kernel<FP>, hipFuncAttributeMaxDynamicSharedMemorySize,
-                            (int)fwd_lds_bytes(FP));
-  (void)hipFuncSetAttribute((const void*)fwdbwd_rows_kernel<FP>, hipFuncAttributeMaxDynamicSharedMemorySize,
-                            (int)fwd_lds_bytes(FP));
-  if constexpr (FP <= 1024)
-    (void)hipFuncSetAttribute((const void*)fwdbwd_rows_kernel<FP, true>, hipFuncAttributeMaxDynamicSharedMemorySize,
-                              (int)fwdbwd_rows_lds_bytes(FP, true));
-  const int b = (int)bwd_ride_lds_bytes(FP);
-  (void)hipFuncSetAttribute((const void*)bwd_update_kernel<FP, 2>, hipFuncAttributeMaxDynamicSharedMemorySize, b);
-  (void)hipFuncSetAttribute((const void*)bwd_update_kernel<FP, 4>, hipFuncAttributeMaxDynamicSharedMemorySize, b);
-  (void)hipFuncSetAttribute((const void*)bwd_update_kernel<FP, 8>, hipFuncAttributeMaxDynamicSharedMemorySize, b);
-  (void)hipFuncSetAttribute((const void*)bwd_update_kernel<FP, 16>, hipFuncAttributeMaxDynamicSharedMemorySize, b);
-}
-
+// Each loop below ranges over the list its launch above dispatches on.
 void prepare_solve_kernels() {
   static bool done = false;
   if (done) return;
-  set_slot_attr<128>();
-  set_slot_attr<256>();
-  set_slot_attr<512>();
-  set_slot_attr<1024>();
-  set_slot_attr<2048>();
-  set_persist_attr<128>();
-  set_persist_attr<256>();
-  set_persist_attr<512>();
-  set_persist_attr<1024>();
+  constexpr hipFuncAttribute kDyn = hipFuncAttributeMaxDynamicSharedMemorySize;
+  for_each_fp([&](auto fp) {
+    (void)hipFuncSetAttribute((const void*)fwd_kernel<fp()>, kDyn, (int)fwd_lds_bytes(fp()));
+    (void)hipFuncSetAttribute((const void*)fwdbwd_rows_kernel<fp()>, kDyn, (int)fwd_lds_bytes(fp()));
+    for_each_int<2, 4, 8, 16>([&](auto kp) {
+      (void)hipFuncSetAttribute((const void*)tail_kernel<fp(), kp()>, kDyn, (int)tail_lds_bytes(fp()));
+      (void)hipFuncSetAttribute((const void*)bwd_update_kernel<fp(), kp()>, kDyn, (int)bwd_ride_lds_bytes(fp()));
+    });
+  });
+  for_each_int<128, 256, 512, 1024>([&](auto fp) {
+    (void)hipFuncSetAttribute((const void*)fwdbwd_rows_kernel<fp(), true>, kDyn,
+                              (int)fwdbwd_rows_lds_bytes(fp(), true));
+    for_each_int<2, 4, 8>([&](auto kp) {
+      (void)hipFuncSetAttribute((const void*)solve_persist_kernel<fp(), kp(), 1>, kDyn, (int)persist_lds_bytes(fp()));
+      (void)hipFuncSetAttribute((const void*)solve_persist_kernel<fp(), kp(), 2>, kDyn, (int)persist_lds_bytes(fp()));
+    });
+  });
   done = true;
 }
 

@@ -30,6 +30,7 @@
 // a fit is bit-reproducible.  No atomics, no cross-workgroup waits.
 #include <hip/hip_runtime.h>
 
+#include "dispatch.h"
 #include "fit_body.h"
 #include "wide_fit_kernels.h"
 #include "wide_row.h"
@@ -378,41 +379,22 @@ void launch_wide_fit_begin(const WideFitDev& dv, const float* w0, int zero_const
   wide_fit_begin_kernel<<<blocks_of(dv.n, 256, INT64_MAX), 256, 0, s>>>(dv, w0, zero_const, raw);
 }
 
-#define PSX_WF_KP(CALL) \
-  switch (dv.KP) {      \
-    case 1: CALL(1);    \
-    case 2: CALL(2);    \
-    case 4: CALL(4);    \
-    case 8: CALL(8);    \
-    case 16: CALL(16);  \
-    default: break;     \
-  }
+static const char kWideFitKP[] = "wide fit: padded classes";
 
 void launch_wide_fit_rows(const WideFitDev& dv, int G, hipStream_t s) {
-#define PSX_WF_ROWS(KV)                                \
-  wide_fit_rows_kernel<KV><<<G, 256, 0, s>>>(dv); \
-  break
-  PSX_WF_KP(PSX_WF_ROWS)
-#undef PSX_WF_ROWS
+  dispatch_wide_kp(kWideFitKP, dv.KP, [&](auto kp) { wide_fit_rows_kernel<kp()><<<G, 256, 0, s>>>(dv); });
 }
 
 void launch_wide_fit_cols(const WideFitDev& dv, hipStream_t s) {
-  if (dv.n_short > 0) {
-#define PSX_WF_SHORT(KV)                                                                             \
-  wide_fit_cols_short_kernel<KV><<<blocks_of(dv.n_short, 256 / KV, 1 << 16), 256, 0, s>>>(dv); \
-  break
-    PSX_WF_KP(PSX_WF_SHORT)
-#undef PSX_WF_SHORT
-  }
-  if (dv.n_long > 0) {
-#define PSX_WF_LONG(KV)                                                                  \
-  wide_fit_cols_long_kernel<KV><<<blocks_of(dv.n_long, 4, 1 << 16), 256, 0, s>>>(dv); \
-  break
-    PSX_WF_KP(PSX_WF_LONG)
-#undef PSX_WF_LONG
-  }
+  if (dv.n_short > 0)
+    dispatch_wide_kp(kWideFitKP, dv.KP, [&](auto kp) {
+      wide_fit_cols_short_kernel<kp()><<<blocks_of(dv.n_short, 256 / kp(), 1 << 16), 256, 0, s>>>(dv);
+    });
+  if (dv.n_long > 0)
+    dispatch_wide_kp(kWideFitKP, dv.KP, [&](auto kp) {
+      wide_fit_cols_long_kernel<kp()><<<blocks_of(dv.n_long, 4, 1 << 16), 256, 0, s>>>(dv);
+    });
 }
-#undef PSX_WF_KP
 
 int wide_fit_reduce_grid(int n) { return (int)blocks_of(n, 256, kWideReduceMaxWG); }
 

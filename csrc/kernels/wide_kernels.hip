@@ -8,6 +8,7 @@
 #include <hip/hip_runtime.h>
 
 #include "common.h"
+#include "dispatch.h"
 #include "wide_kernels.h"
 #include "wide_row.h"
 
@@ -1004,30 +1005,26 @@ void wide_launch_prepare(const WideCfg& c, const WideDev& d, hipStream_t s) {
   wide_prep_kernel<<<grid_for(d.PLmax, 1024), 256, 0, s>>>(c, d);
 }
 
-template <int KP>
-static void launch_fwdbwd_kp(const WideCfg& c, const WideDev& d, int slot, int grid, hipStream_t s) {
-  const int nq = (c.NZ + 63) / 64;
-  const int thr = 64 * d.RB;
-  const size_t lds = (size_t)d.EB * KP * 4;
-  if (nq <= 1)
-    wide_fwdbwd_kernel<KP, 1><<<grid, thr, lds, s>>>(c, d, slot);
-  else if (nq <= 2)
-    wide_fwdbwd_kernel<KP, 2><<<grid, thr, lds, s>>>(c, d, slot);
-  else if (nq <= 4)
-    wide_fwdbwd_kernel<KP, 4><<<grid, thr, lds, s>>>(c, d, slot);
-  else
-    wide_fwdbwd_kernel<KP, 8><<<grid, thr, lds, s>>>(c, d, slot);
+// The solve kernels' two template parameters: the padded class count and the quarter-waves
+// per ring row (wide_quarters of dispatch.h).  f(kp, nq) gets both as constants.
+template <class F>
+static void dispatch_kp_nq(const WideCfg& c, F&& f) {
+  dispatch_wide_kp("wide solve: padded classes", c.KP, [&](auto kp) {
+    dispatch_int<1, 2, 4, 8>("wide solve: quarter-waves per row", wide_quarters(c.NZ), [&](auto nq) { f(kp, nq); });
+  });
+}
+template <class F>
+static void for_each_kp_nq(F&& f) {
+  for_each_wide_kp([&](auto kp) { for_each_int<1, 2, 4, 8>([&](auto nq) { f(kp, nq); }); });
 }
 
 void wide_launch_slot(const WideCfg& c, const WideDev& d, int slot, int nblk_dots, hipStream_t s) {
   const int rows_grid = ngroups(c, d);  // one workgroup per group of RB rows
-  switch (c.KP) {
-    case 1: launch_fwdbwd_kp<1>(c, d, slot, rows_grid, s); break;
-    case 2: launch_fwdbwd_kp<2>(c, d, slot, rows_grid, s); break;
-    case 4: launch_fwdbwd_kp<4>(c, d, slot, rows_grid, s); break;
-    case 8: launch_fwdbwd_kp<8>(c, d, slot, rows_grid, s); break;
-    default: launch_fwdbwd_kp<16>(c, d, slot, rows_grid, s); break;
-  }
+  const int thr = 64 * d.RB;
+  const size_t lds = (size_t)d.EB * c.KP * 4;
+  dispatch_kp_nq(c, [&](auto kp, auto nq) {
+    wide_fwdbwd_kernel<kp(), nq()><<<rows_grid, thr, lds, s>>>(c, d, slot);
+  });
   wide_dots_kernel<<<nblk_dots, 256, 0, s>>>(c, d, slot);
   wide_apply_kernel<<<grid_for(d.PLmax, 1024), 256, 0, s>>>(c, d, slot);
 }
@@ -1037,60 +1034,21 @@ int wide_tail_grid(const WideCfg& c, const WideDev& d) {
   return g < 64 ? g : 64;
 }
 
-template <int KP>
-static void launch_tail_kp(const WideCfg& c, const WideDev& d, int s0, int s1, hipStream_t s) {
-  const int nq = (c.NZ + 63) / 64;
-  const int G = wide_tail_grid(c, d);
-  const size_t lds = (size_t)d.EB * KP * 4;
-  if (nq <= 1)
-    wide_tail_kernel<KP, 1><<<G, 512, lds, s>>>(c, d, s0, s1);
-  else if (nq <= 2)
-    wide_tail_kernel<KP, 2><<<G, 512, lds, s>>>(c, d, s0, s1);
-  else if (nq <= 4)
-    wide_tail_kernel<KP, 4><<<G, 512, lds, s>>>(c, d, s0, s1);
-  else
-    wide_tail_kernel<KP, 8><<<G, 512, lds, s>>>(c, d, s0, s1);
-}
-
 void wide_launch_tail(const WideCfg& c, const WideDev& d, int s0, int s1, hipStream_t s) {
-  switch (c.KP) {
-    case 1: launch_tail_kp<1>(c, d, s0, s1, s); break;
-    case 2: launch_tail_kp<2>(c, d, s0, s1, s); break;
-    case 4: launch_tail_kp<4>(c, d, s0, s1, s); break;
-    case 8: launch_tail_kp<8>(c, d, s0, s1, s); break;
-    default: launch_tail_kp<16>(c, d, s0, s1, s); break;
-  }
+  const int G = wide_tail_grid(c, d);
+  const size_t lds = (size_t)d.EB * c.KP * 4;
+  dispatch_kp_nq(c, [&](auto kp, auto nq) { wide_tail_kernel<kp(), nq()><<<G, 512, lds, s>>>(c, d, s0, s1); });
 }
 
-template <int KP, int NQ>
-static void set_tail_attr() {
-  (void)hipFuncSetAttribute((const void*)wide_tail_kernel<KP, NQ>, hipFuncAttributeMaxDynamicSharedMemorySize,
-                            96 * 1024);
-}
-template <int KP, int NQ>
-static void set_persist_attr() {
-  (void)hipFuncSetAttribute((const void*)wide_persist_kernel<KP, NQ>, hipFuncAttributeMaxDynamicSharedMemorySize,
-                            96 * 1024);
-}
-template <int KP>
-static void set_tail_attr_kp() {
-  set_tail_attr<KP, 1>();
-  set_tail_attr<KP, 2>();
-  set_tail_attr<KP, 4>();
-  set_tail_attr<KP, 8>();
-  set_persist_attr<KP, 1>();
-  set_persist_attr<KP, 2>();
-  set_persist_attr<KP, 4>();
-  set_persist_attr<KP, 8>();
-}
 void wide_prepare_kernels() {
   static bool done = false;
   if (done) return;
-  set_tail_attr_kp<1>();
-  set_tail_attr_kp<2>();
-  set_tail_attr_kp<4>();
-  set_tail_attr_kp<8>();
-  set_tail_attr_kp<16>();
+  for_each_kp_nq([](auto kp, auto nq) {
+    (void)hipFuncSetAttribute((const void*)wide_tail_kernel<kp(), nq()>, hipFuncAttributeMaxDynamicSharedMemorySize,
+                              96 * 1024);
+    (void)hipFuncSetAttribute((const void*)wide_persist_kernel<kp(), nq()>, hipFuncAttributeMaxDynamicSharedMemorySize,
+                              96 * 1024);
+  });
   done = true;
 }
 
@@ -1102,29 +1060,12 @@ size_t wide_persist_lds(const WideCfg& c, const WideDev& d) {
 
 int wide_persist_grid() { return 256; }
 
-template <int KP>
-static void launch_persist_kp(const WideCfg& c, const WideDev& d, int B, int start, int phases, hipStream_t s) {
-  const int nq = (c.NZ + 63) / 64;
+void wide_launch_persist(const WideCfg& c, const WideDev& d, int B, int start, int phases, hipStream_t s) {
   const size_t lds = wide_persist_lds(c, d);
   const int G = wide_persist_grid();
-  if (nq <= 1)
-    wide_persist_kernel<KP, 1><<<G, 512, lds, s>>>(c, d, B, start, phases);
-  else if (nq <= 2)
-    wide_persist_kernel<KP, 2><<<G, 512, lds, s>>>(c, d, B, start, phases);
-  else if (nq <= 4)
-    wide_persist_kernel<KP, 4><<<G, 512, lds, s>>>(c, d, B, start, phases);
-  else
-    wide_persist_kernel<KP, 8><<<G, 512, lds, s>>>(c, d, B, start, phases);
-}
-
-void wide_launch_persist(const WideCfg& c, const WideDev& d, int B, int start, int phases, hipStream_t s) {
-  switch (c.KP) {
-    case 1: launch_persist_kp<1>(c, d, B, start, phases, s); break;
-    case 2: launch_persist_kp<2>(c, d, B, start, phases, s); break;
-    case 4: launch_persist_kp<4>(c, d, B, start, phases, s); break;
-    case 8: launch_persist_kp<8>(c, d, B, start, phases, s); break;
-    default: launch_persist_kp<16>(c, d, B, start, phases, s); break;
-  }
+  dispatch_kp_nq(c, [&](auto kp, auto nq) {
+    wide_persist_kernel<kp(), nq()><<<G, 512, lds, s>>>(c, d, B, start, phases);
+  });
 }
 
 // 8 XCDs x 32 lanes' workgroups, twice over: an XCD the dispatcher deals fewer than
@@ -1237,55 +1178,27 @@ static int lanes_per_cu_kp(size_t lds) {
 }
 
 int wide_lanes_per_cu(const WideCfg& c, size_t lds) {
-  const int nq = (c.NZ + 63) / 64;
-#define PSX_OCC(KV)                                                                                          \
-  case KV:                                                                                                   \
-    return nq <= 1 ? lanes_per_cu_kp<KV, 1>(lds)                                                             \
-                   : (nq <= 2 ? lanes_per_cu_kp<KV, 2>(lds)                                                  \
-                              : (nq <= 4 ? lanes_per_cu_kp<KV, 4>(lds) : lanes_per_cu_kp<KV, 8>(lds)));
-  switch (c.KP) {
-    PSX_OCC(1)
-    PSX_OCC(2)
-    PSX_OCC(4)
-    PSX_OCC(8)
-    default:
-      PSX_OCC(16)
-  }
-#undef PSX_OCC
-}
-
-template <int KP, int NQ>
-static void set_lanes_attr() {
-  (void)hipFuncSetAttribute((const void*)wide_lanes_kernel<KP, NQ>, hipFuncAttributeMaxDynamicSharedMemorySize,
-                            96 * 1024);
+  int n = 1;
+  dispatch_kp_nq(c, [&](auto kp, auto nq) { n = lanes_per_cu_kp<kp(), nq()>(lds); });
+  return n;
 }
 
 template <int KP>
-static void launch_lanes_kp(const WideCfg& c, const WideDev* devs, const WideLanesArgs& a, size_t lds,
-                            hipStream_t s) {
-  static const bool prepared = (set_lanes_attr<KP, 1>(), set_lanes_attr<KP, 2>(), set_lanes_attr<KP, 4>(),
-                                set_lanes_attr<KP, 8>(), true);
+static void prepare_lanes_kp() {  // on the first launch of a class count, as before: its four NQ forms
+  static const bool prepared = (for_each_int<1, 2, 4, 8>([](auto nq) {
+                                  (void)hipFuncSetAttribute((const void*)wide_lanes_kernel<KP, nq()>,
+                                                            hipFuncAttributeMaxDynamicSharedMemorySize, 96 * 1024);
+                                }),
+                                true);
   (void)prepared;
-  const int nq = (c.NZ + 63) / 64;
-  const int G = wide_lanes_grid(a.gpx);
-  if (nq <= 1)
-    wide_lanes_kernel<KP, 1><<<G, 512, lds, s>>>(c, devs, a);
-  else if (nq <= 2)
-    wide_lanes_kernel<KP, 2><<<G, 512, lds, s>>>(c, devs, a);
-  else if (nq <= 4)
-    wide_lanes_kernel<KP, 4><<<G, 512, lds, s>>>(c, devs, a);
-  else
-    wide_lanes_kernel<KP, 8><<<G, 512, lds, s>>>(c, devs, a);
 }
 
 void wide_launch_lanes(const WideCfg& c, const WideDev* devs, const WideLanesArgs& a, size_t lds, hipStream_t s) {
-  switch (c.KP) {
-    case 1: launch_lanes_kp<1>(c, devs, a, lds, s); break;
-    case 2: launch_lanes_kp<2>(c, devs, a, lds, s); break;
-    case 4: launch_lanes_kp<4>(c, devs, a, lds, s); break;
-    case 8: launch_lanes_kp<8>(c, devs, a, lds, s); break;
-    default: launch_lanes_kp<16>(c, devs, a, lds, s); break;
-  }
+  const int G = wide_lanes_grid(a.gpx);
+  dispatch_kp_nq(c, [&](auto kp, auto nq) {
+    prepare_lanes_kp<kp()>();
+    wide_lanes_kernel<kp(), nq()><<<G, 512, lds, s>>>(c, devs, a);
+  });
 }
 
 void wide_launch_finalize(const WideCfg& c, const WideDev& d, hipStream_t s) {
@@ -1786,25 +1699,14 @@ void launch_wide_eval(int K, int KP, int64_t F, const int64_t* indptr, const int
   char* sl = static_cast<char*>(slot);
   char* sl2 = static_cast<char*>(slot2);
   const bool pair = sl2 != nullptr;
-#define PSX_WE(KV)                                                                                             \
-  case KV:                                                                                                     \
-    if (pair)                                                                                                  \
-      wide_eval_kernel<KV, true><<<grid, 256, 0, s>>>(K, F, indptr, idx, val, y, T, w, htab, hmask, wloc, acc, \
-                                                      ticket, sl, loss, seq, sl2, seq2, nullptr, nullptr);     \
-    else                                                                                                        \
-      wide_eval_kernel<KV, false><<<grid, 256, 0, s>>>(K, F, indptr, idx, val, y, T, w, htab, hmask, wloc, acc, \
-                                                       ticket, sl, loss, seq, nullptr, 0, zbase, bias);        \
-    break;
-  switch (KP) {
-    PSX_WE(1)
-    PSX_WE(2)
-    PSX_WE(4)
-    PSX_WE(8)
-    PSX_WE(16)
-    default:
-      break;
-  }
-#undef PSX_WE
+  dispatch_wide_kp("wide_eval: padded classes", KP, [&](auto kp) {
+    if (pair)
+      wide_eval_kernel<kp(), true><<<grid, 256, 0, s>>>(K, F, indptr, idx, val, y, T, w, htab, hmask, wloc, acc,
+                                                        ticket, sl, loss, seq, sl2, seq2, nullptr, nullptr);
+    else
+      wide_eval_kernel<kp(), false><<<grid, 256, 0, s>>>(K, F, indptr, idx, val, y, T, w, htab, hmask, wloc, acc,
+                                                         ticket, sl, loss, seq, nullptr, 0, zbase, bias);
+  });
 }
 
 void launch_wide_eval_multi(int K, int KP, int64_t F, const int64_t* indptr, const int32_t* idx, const uint16_t* val,
@@ -1812,20 +1714,9 @@ void launch_wide_eval_multi(int K, int KP, int64_t F, const int64_t* indptr, con
                             unsigned* ticket, hipStream_t s) {
   if (T <= 0 || m.nov + m.plain <= 0) return;
   const int grid = grid_for((int64_t)T * 16, 1024);  // 16 rows per workgroup pass
-#define PSX_WM(KV)                                                                                         \
-  case KV:                                                                                                 \
-    wide_eval_multi_kernel<KV><<<grid, 256, 0, s>>>(K, F, indptr, idx, val, y, T, w, m, acc, ticket); \
-    break;
-  switch (KP) {
-    PSX_WM(1)
-    PSX_WM(2)
-    PSX_WM(4)
-    PSX_WM(8)
-    PSX_WM(16)
-    default:
-      break;
-  }
-#undef PSX_WM
+  dispatch_wide_kp("wide_eval_multi: padded classes", KP, [&](auto kp) {
+    wide_eval_multi_kernel<kp()><<<grid, 256, 0, s>>>(K, F, indptr, idx, val, y, T, w, m, acc, ticket);
+  });
 }
 
 void launch_wide_logits(int K, int KP, int64_t F, const int64_t* indptr, const int32_t* idx, const uint16_t* val,
@@ -1833,20 +1724,9 @@ void launch_wide_logits(int K, int KP, int64_t F, const int64_t* indptr, const i
   (void)K;
   if (T <= 0) return;
   const int grid = grid_for((int64_t)T * 64, 1024);
-#define PSX_WL(KV)                                                                      \
-  case KV:                                                                              \
-    wide_logits_kernel<KV><<<grid, 256, 0, s>>>(F, indptr, idx, val, T, w, out); \
-    break;
-  switch (KP) {
-    PSX_WL(1)
-    PSX_WL(2)
-    PSX_WL(4)
-    PSX_WL(8)
-    PSX_WL(16)
-    default:
-      break;
-  }
-#undef PSX_WL
+  dispatch_wide_kp("wide_logits: padded classes", KP, [&](auto kp) {
+    wide_logits_kernel<kp()><<<grid, 256, 0, s>>>(F, indptr, idx, val, T, w, out);
+  });
 }
 
 // ---------------------------------------------------------------------------

@@ -14,6 +14,7 @@
 #include <string>
 #include <thread>
 
+#include "../kernels/dispatch.h"
 #include "../kernels/lr_kernels.h"
 #include "../kernels/wide_kernels.h"
 #include "../solver/solver.h"
@@ -342,6 +343,12 @@ AsyncServer::AsyncServer(P2P* comm, const AsyncServerCfg& cfg, hipStream_t strea
   if (cfg.model == kAsyncDense && cfg.sink && !cfg.cpu && (!cfg.fhi || !cfg.flo || !cfg.fb || !cfg.Xt || !cfg.yt))
     throw std::invalid_argument("AsyncServer: dense evaluation needs fragments and a test set");
   if (cfg.sink && (!cfg.acc || !cfg.ticket)) throw std::invalid_argument("AsyncServer: evaluation scratch");
+  if (cfg.sink && !cfg.cpu) {  // what the evaluation's launch would refuse at the first logged token
+    if (cfg.model == kAsyncDense)
+      dispatch_fp("AsyncServer: padded width", cfg.FP, [](auto) {});
+    else
+      dispatch_wide_kp("AsyncServer: padded classes", cfg.KP, [](auto) {});
+  }
   if (!cfg.peer.empty() && (int)cfg.peer.size() != cfg.nworkers)
     throw std::invalid_argument("AsyncServer: one peer per worker");
   if (!cfg.replies.empty() && (int)cfg.replies.size() != cfg.nworkers)

@@ -41,6 +41,7 @@
 #include "../host/sampling.h"
 #include "../host/server_protocol.h"
 #include "../host/tracker.h"
+#include "../kernels/dispatch.h"
 #include "../solver/fit_loop.h"
 
 using namespace psx;
@@ -1643,7 +1644,71 @@ static void test_fit_loop() {
   }
 }
 
+// dispatch.h: a run-time value reaches the functor as the matching compile-time
+// constant exactly once; a value outside the list throws and calls nothing.
+static void test_dispatch() {
+  const int list[] = {128, 256, 512, 1024, 2048};
+  for (int v : list) {  // every listed value, the first, a middle one and the last among them
+    int calls = 0, got = 0;
+    dispatch_int<128, 256, 512, 1024, 2048>("width", v, [&](auto c) {
+      static_assert(std::is_same<decltype(c), std::integral_constant<int, c()>>::value, "a constant, not an int");
+      ++calls;
+      got = c();
+    });
+    CHECK(calls == 1 && got == v);
+    calls = got = 0;
+    dispatch_fp("width", v, [&](auto c) {
+      ++calls;
+      got = c();
+    });
+    CHECK(calls == 1 && got == v);
+  }
+  for (int kp : {1, 2, 4, 8, 16}) {  // nested: the pair arrives together
+    int calls = 0, gf = 0, gk = 0;
+    dispatch_fp("width", 512, [&](auto fp) {
+      dispatch_wide_kp("classes", kp, [&](auto k) {
+        constexpr int product = fp() * k();  // both usable as template arguments in there
+        ++calls;
+        gf = fp();
+        gk = product / fp();
+      });
+    });
+    CHECK(calls == 1 && gf == 512 && gk == kp);
+  }
+  for (int v : {0, -1, 3, 127, 192, 2047, 4096}) {
+    int calls = 0;
+    const std::string e =
+        error_of<std::invalid_argument>([&] { dispatch_fp("fit: padded width", v, [&](auto) { ++calls; }); });
+    CHECK(calls == 0);
+    CHECK(e.find("fit: padded width") != std::string::npos && e.find(std::to_string(v)) != std::string::npos);
+  }
+  {  // an inner value outside its list: the outer functor ran, the inner did not
+    int outer = 0, inner = 0;
+    const std::string e = error_of<std::invalid_argument>([&] {
+      dispatch_fp("width", 128, [&](auto) {
+        ++outer;
+        dispatch_int<2, 4, 8>("classes", 16, [&](auto) { ++inner; });
+      });
+    });
+    CHECK(outer == 1 && inner == 0 && e.find("classes") != std::string::npos && e.find("16") != std::string::npos);
+  }
+  std::vector<int> seen;
+  for_each_int<2, 4, 8, 16>([&](auto c) { seen.push_back(c()); });
+  CHECK((seen == std::vector<int>{2, 4, 8, 16}));
+  seen.clear();
+  for_each_fp([&](auto c) { seen.push_back(c()); });
+  CHECK((seen == std::vector<int>(list, list + 5)));
+  seen.clear();
+  for_each_wide_kp([&](auto c) { seen.push_back(c()); });
+  CHECK((seen == std::vector<int>{1, 2, 4, 8, 16}));
+  // the wide solver's quarter-waves per ring row
+  const int nz[] = {1, 64, 65, 129, 256, 257, 512}, nq[] = {1, 1, 2, 4, 4, 8, 8};
+  for (int i = 0; i < 7; ++i) CHECK(wide_quarters(nz[i]) == nq[i]);
+  CHECK(wide_quarters(128) == 2 && wide_quarters(513) == 16);  // (past the widest ring: no listed value)
+}
+
 int main() {
+  test_dispatch();
   test_tracker();
   test_tracker_faults();
   test_libsvm();
