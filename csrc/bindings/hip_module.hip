@@ -393,7 +393,22 @@ PYBIND11_MODULE(_psx_hip, m) {
           py::arg("X"), py::arg("y"), py::arg("N"), py::arg("Npad"), py::arg("stream") = 0)
       .def(
           "read_std", [](BatchFitter& f, uintptr_t out, uintptr_t stream) { f.read_std(P<float>(out), S(stream)); },
-          py::arg("out"), py::arg("stream") = 0);
+          py::arg("out"), py::arg("stream") = 0)
+      .def(
+          "set_weights",
+          [](BatchFitter& f, uintptr_t sample_weight, const std::vector<float>& class_weight, uintptr_t fold,
+             int holdout, uintptr_t stream) {
+            if (!class_weight.empty() && (int)class_weight.size() != f.classes())
+              throw std::invalid_argument("set_weights: one class weight per class");
+            f.set_weights(P<const float>(sample_weight), class_weight.empty() ? nullptr : class_weight.data(),
+                          P<const uint8_t>(fold), holdout, S(stream));
+          },
+          py::arg("sample_weight") = 0, py::arg("class_weight") = std::vector<float>{}, py::arg("fold") = 0,
+          py::arg("holdout") = -1, py::arg("stream") = 0)
+      .def_property_readonly("weighted", &BatchFitter::weighted)
+      .def(
+          "holdout_loss", [](BatchFitter& f, uintptr_t stream) { return f.holdout_loss(S(stream)); },
+          py::arg("stream") = 0);
   py::class_<WideBatchFitter, FitDriver>(m, "WideBatchFitter")
       .def(py::init<int, int, int, int>(), py::arg("K"), py::arg("KP"), py::arg("hist") = 10, py::arg("max_wg") = 0)
       .def(

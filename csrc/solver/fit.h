@@ -14,6 +14,7 @@
 #include <stdint.h>
 
 #include "../kernels/fit_kernels.h"
+#include "../kernels/fit_weighted.h"
 #include "fit_driver.h"
 
 namespace psx {
@@ -28,6 +29,19 @@ class BatchFitter : public FitDriver {
   // caller-owned, must outlive every later call.  Computes the feature statistics.
   void set_data(const uint16_t* X, const int32_t* y, int64_t N, int64_t Npad, hipStream_t s);
   void read_std(float* std_out, hipStream_t s);  // [FP]
+  // Row weights u_i = sample_weight_i * class_weight[y_i] and a held-out fold (the
+  // objective is stated in csrc/kernels/fit_weighted.h).  sample_weight [Npad] fp32 and
+  // fold [Npad] uint8 are device buffers, caller-owned as the rows are; class_weight is
+  // K host floats; each may be null.  holdout < 0: no row is held out.  Valid after
+  // set_data; ends a fit in progress and computes the weighted statistics.  All null
+  // and holdout < 0: back to the plain kernels and statistics.  A new set_data clears
+  // the weights.
+  void set_weights(const float* sample_weight, const float* class_weight, const uint8_t* fold, int holdout,
+                   hipStream_t s);
+  bool weighted() const { return weighted_; }
+  int classes() const { return dv_.K; }
+  // The held-out rows' weighted mean loss at the last evaluation (0 without held-out weight).
+  double holdout_loss(hipStream_t s);
 
  protected:
   // the weights are [K*FP + K]; the vectors exist from construction
@@ -41,6 +55,8 @@ class BatchFitter : public FitDriver {
 
  private:
   FitDev dv_{};
+  FitWeightsDev wd_{};
+  bool weighted_ = false;
   void* ws_ = nullptr;
   void* data_ws_ = nullptr;  // per-dataset partials (sized by the grid)
 };

@@ -23,6 +23,7 @@ BatchFitter::BatchFitter(int K, int F, int FP, int hist, int max_wg) : FitDriver
     carve_fit_vectors(c, dv_, fit_reduce_grid(dv_.n));
     c.take(dv_.std_, FP), c.take(dv_.inv_std, FP), c.take(dv_.b_eff, 16);
     c.take(dv_.whi, (size_t)16 * FP), c.take(dv_.wlo, (size_t)16 * FP);
+    c.take(wd_.wsum, 2), c.take(wd_.ho, 1);
   };
   Carver size;
   layout(size);
@@ -31,6 +32,7 @@ BatchFitter::BatchFitter(int K, int F, int FP, int hist, int max_wg) : FitDriver
   Carver place{static_cast<char*>(ws_)};
   layout(place);
   prepare_fit_kernels();
+  prepare_fit_weighted_kernels();
 }
 
 BatchFitter::~BatchFitter() {
@@ -43,6 +45,10 @@ void BatchFitter::set_data(const uint16_t* X, const int32_t* y, int64_t N, int64
   if (Npad != (N + 31) / 32 * 32) throw std::invalid_argument("the rows must be padded to a multiple of 32");
   if (!X || !y) throw std::invalid_argument("null rows or labels");
   end_fit();
+  weighted_ = false;
+  wd_.sw = nullptr;
+  wd_.fold = nullptr;
+  wd_.holdout = -1;
   dv_.X = X;
   dv_.y = y;
   dv_.N = (int)N;
@@ -57,6 +63,7 @@ void BatchFitter::set_data(const uint16_t* X, const int32_t* y, int64_t N, int64
   const size_t G = G_;
   auto layout = [&](Carver& c) {
     c.take(dv_.gpart, G * dv_.K * dv_.FP), c.take(dv_.part, G * 32), c.take(dv_.spart, G * 2 * dv_.FP);
+    c.take(wd_.wpart, G * 2), c.take(wd_.mmpart, G * 2 * dv_.FP);
   };
   Carver size;
   layout(size);
@@ -65,6 +72,37 @@ void BatchFitter::set_data(const uint16_t* X, const int32_t* y, int64_t N, int64
   layout(place);
   launch_fit_stats(dv_, G_, s);
   hip_check(hipGetLastError(), "fit_stats launch");
+}
+
+void BatchFitter::set_weights(const float* sample_weight, const float* class_weight, const uint8_t* fold, int holdout,
+                              hipStream_t s) {
+  if (!dv_.X) throw std::runtime_error("set_weights: no dataset (set_data first)");
+  if (holdout > 255) throw std::invalid_argument("set_weights: fold ids are 0..255");
+  if (holdout >= 0 && !fold) throw std::invalid_argument("set_weights: a held-out fold needs fold ids");
+  end_fit();
+  if (!sample_weight && !class_weight && holdout < 0) {
+    if (weighted_) {  // sigma is the weighted one: the plain statistics again
+      launch_fit_stats(dv_, G_, s);
+      hip_check(hipGetLastError(), "fit_stats launch");
+    }
+    weighted_ = false;
+    return;
+  }
+  wd_.sw = sample_weight;
+  wd_.fold = fold;
+  wd_.holdout = holdout < 0 ? -1 : holdout;
+  for (int c = 0; c < 16; ++c) wd_.cw[c] = c < dv_.K ? (class_weight ? class_weight[c] : 1.f) : 0.f;
+  weighted_ = true;
+  launch_fit_stats_w(dv_, wd_, G_, s);
+  hip_check(hipGetLastError(), "fit_stats_w launch");
+}
+
+double BatchFitter::holdout_loss(hipStream_t s) {
+  if (!weighted_) throw std::runtime_error("holdout_loss: no weights (set_weights first)");
+  double v = 0.0;
+  hip_check(hipMemcpyAsync(&v, wd_.ho, sizeof(double), hipMemcpyDeviceToHost, s), "hipMemcpyAsync(held-out loss)");
+  hip_check(hipStreamSynchronize(s), "hipStreamSynchronize(held-out loss)");
+  return v;
 }
 
 FitVectors BatchFitter::vectors() const {
@@ -76,6 +114,11 @@ void BatchFitter::launch_begin(const float* w0, int zero_const, int raw, hipStre
 }
 
 void BatchFitter::launch_eval(double reg, int raw, hipStream_t s) {
+  if (weighted_) {
+    launch_fit_lossgrad_w(dv_, wd_, G_, s);
+    launch_fit_reduce_w(dv_, wd_, G_, reg, raw, s);
+    return;
+  }
   launch_fit_lossgrad(dv_, G_, s);
   launch_fit_reduce(dv_, G_, reg, raw, s);
 }

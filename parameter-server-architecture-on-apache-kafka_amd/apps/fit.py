@@ -3,6 +3,7 @@
 Usage: python -m psx.apps.fit --train train.csv [--test test.csv] [--valid valid.csv | --valid_frac 0.1 --seed 0]
            [--reg_param 0] [--max_iter 100] [--tol 1e-6] [--init_checkpoint DIR] [--checkpoint_dir OUT]
            [--device ...] [--header auto|yes|no] [--label_col -1] [--num_classes K]
+           [--class_weight balanced|w0,w1,...] [--cv K --reg_params a,b,c]
        python -m psx.apps.fit --train train.svm [--num_features F] [--sigmoid] [--zero_based] [...]
 
 CSVs and binary row caches fit the dense model.  A LIBSVM file (``.svm``, ``.libsvm``,
@@ -10,7 +11,11 @@ CSVs and binary row caches fit the dense model.  A LIBSVM file (``.svm``, ``.lib
 largest training id + 1); ``--sigmoid`` selects the one-logit model with labels {0, 1},
 ``--zero_based`` files whose feature ids start at 0.  ``--valid`` / ``--valid_frac`` score
 the iterates on held-out rows and keep the best one (``--patience N`` stops after N checks
-without improvement).  ``--checkpoint_dir`` gets a ``server.ckpt`` that
+without improvement).  Dense model only: ``--class_weight`` weighs the rows by their class
+(``balanced``: N / (classes present * class count)); ``--cv K --reg_params a,b,c`` runs a
+K-fold cross-validation of the penalties on the resident rows, prints its table to stderr
+and fits the whole set at the best one (it excludes ``--valid`` / ``--valid_frac``).
+``--checkpoint_dir`` gets a ``server.ckpt`` that
 ``python -m psx.apps.predict`` reads.  stdout gets one JSON line: rows, features,
 classes, iterations, evaluations, reason, objective, train log-loss, the test metrics
 (through the Scorer) and the fit's seconds; a wide fit adds ``touched_features``.
@@ -48,6 +53,9 @@ def fit_parser():
     ap.add_argument("--num_features", type=int, default=None, help="wide model: F (default: largest training id + 1)")
     ap.add_argument("--sigmoid", action="store_true", help="wide model: one logit, labels {0, 1}")
     ap.add_argument("--zero_based", action="store_true", help="LIBSVM feature ids start at 0")
+    ap.add_argument("--class_weight", default=None, help="dense model: 'balanced' or one weight per class, w0,w1,...")
+    ap.add_argument("--cv", type=int, default=0, help="dense model: folds of a cross-validation over --reg_params")
+    ap.add_argument("--reg_params", default=None, help="penalties --cv compares, a,b,c")
     return ap
 
 
@@ -71,9 +79,13 @@ def main(argv=None) -> int:
         ap.error("--valid and --valid_frac exclude each other")
     if not 0.0 <= a.valid_frac < 1.0:
         ap.error("--valid_frac must be in [0, 1)")
+    if a.cv and (a.valid or a.valid_frac):
+        ap.error("--cv excludes --valid and --valid_frac")
+    if bool(a.cv) != bool(a.reg_params):
+        ap.error("--cv and --reg_params go together")
     from ..models.logreg import ModelSpec
     from ..models.wide import WideSpec
-    from ..ops.fit import BatchFitter, FitOptions
+    from ..ops.fit import BatchFitter, FitOptions, FitWeights, cross_validate
     from ..ops.score import Scorer
     from ..ops.wide_fit import WideFitter
     from ..utils import data as data_mod
@@ -82,6 +94,8 @@ def main(argv=None) -> int:
     wide = data_mod.is_libsvm_path(a.train)
     if not wide and (a.num_features is not None or a.sigmoid or a.zero_based):
         ap.error("--num_features, --sigmoid and --zero_based go with a LIBSVM --train file (the wide model)")
+    if wide and (a.class_weight or a.cv):
+        ap.error("--class_weight and --cv go with the dense model")
     num_features = a.num_features
 
     def load(path):
@@ -117,17 +131,33 @@ def main(argv=None) -> int:
         if init.wide != wide or init.spec != spec:
             ap.error(f"--init_checkpoint holds {init.spec}, the data needs {spec}")
         w0 = init.w
+    cv = None
     try:
-        opts = FitOptions(max_iter=a.max_iter, tol=a.tol, reg_param=a.reg_param)
+        cw = a.class_weight
+        if cw and cw != "balanced":
+            cw = torch.tensor([float(v) for v in cw.split(",")])
+        reg = a.reg_param
+        if a.cv:
+            regs = [float(v) for v in a.reg_params.split(",")]
+            cv = cross_validate(spec, train, regs, folds=a.cv, seed=a.seed, device=device, class_weight=cw,
+                                opts=FitOptions(max_iter=a.max_iter, tol=a.tol))
+            for r, row, m in zip(cv.reg_params, cv.losses, cv.means):
+                print(f"reg_param {r:<10g} held-out loss " + " ".join(f"{v:.6f}" for v in row) + f"  mean {m:.6f}",
+                      file=sys.stderr)
+            reg = cv.best_reg_param
+        opts = FitOptions(max_iter=a.max_iter, tol=a.tol, reg_param=reg)
         fitter = WideFitter(spec, device, opts) if wide else BatchFitter(spec, device, opts)
-        res = fitter.fit(train, w0=w0, valid=valid, valid_every=a.valid_every, patience=a.patience)
+        extra = {"weights": FitWeights(class_weight=cw)} if cw is not None else {}
+        res = fitter.fit(train, w0=w0, valid=valid, valid_every=a.valid_every, patience=a.patience, **extra)
     except ValueError as e:
         ap.error(str(e))
     if a.checkpoint_dir:
         res.save(a.checkpoint_dir)
     line = {"rows": train.rows, "features": spec.F, "classes": spec.K, "iterations": res.iters,
             "evaluations": res.evals, "reason": res.reason, "objective": res.objective,
-            "train_log_loss": res.log_loss, "reg_param": a.reg_param}
+            "train_log_loss": res.log_loss, "reg_param": reg}
+    if cv is not None:
+        line.update(cv_folds=a.cv, cv_reg_params=cv.reg_params, cv_mean_loss=cv.means)
     if wide:
         line.update(touched_features=int(res.features.numel()))
     if valid is not None:

@@ -66,6 +66,35 @@ def multinomial_loss_grad(X, y, coef_eff, b):
     return loss, (p.t() @ X) / n, p.sum(0) / n
 
 
+def weighted_feature_std(X, u):
+    """Weighted sample std over the rows: ``mean = sum u x / W``, ``var = (sum u x^2 - W
+    mean^2) / (W - 1)``, ``W = sum u`` (two-pass, float64).  Rows of weight 0 do not
+    count: a feature with one value on the rows of positive weight has sigma 0 exactly."""
+    X, u = X.double(), u.double()
+    W = u.sum()
+    live = X[u > 0]
+    if not float(W) > 1.0 or live.shape[0] == 0:
+        return torch.zeros(X.shape[1], dtype=torch.float64)
+    mean = (u @ X) / W
+    sd = ((u @ (X - mean) ** 2) / (W - 1.0)).clamp_min(0).sqrt()
+    return torch.where(live.max(0).values > live.min(0).values, sd, torch.zeros_like(sd))
+
+
+def weighted_loss_grad(X, y, coef_eff, b, u):
+    """``multinomial_loss_grad`` with row weights: ``(1/W) sum u CE`` and its gradients,
+    ``W = sum u`` (0 for all of them when W is 0)."""
+    u = u.to(X.dtype)
+    W = u.sum()
+    if float(W) == 0.0:
+        return torch.zeros((), dtype=X.dtype), torch.zeros_like(coef_eff), torch.zeros_like(b)
+    z = X @ coef_eff.t() + b
+    ce = torch.logsumexp(z, dim=1) - z.gather(1, y.view(-1, 1)).squeeze(1)
+    r = torch.softmax(z, dim=1)
+    r[torch.arange(X.shape[0]), y] -= 1.0
+    r = r * u.view(-1, 1)
+    return (u * ce).sum() / W, (r.t() @ X) / W, r.sum(0) / W
+
+
 def _interp(lt, lf, ld, rt, rf, rd):
     if lt > rt:
         lt, lf, ld, rt, rf, rd = rt, rf, rd, lt, lf, ld

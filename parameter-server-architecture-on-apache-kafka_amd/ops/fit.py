@@ -16,6 +16,16 @@ GPU: every per-row number comes from ``csrc/kernels/fit_kernels.hip`` driven by
 ``csrc/solver/fit.hip`` (a missing extension is a hard error); the whole dataset is
 resident in HBM as bf16 rows.  CPU: :func:`psx.models.reference.fit_reference`.
 
+Row weights and a held-out fold (:class:`FitWeights`, ``weights=`` of
+:meth:`BatchFitter.fit` / :meth:`BatchFitter.loss_grad`): with ``u_i = sample_weight_i *
+class_weight[y_i]`` and ``train = {i : fold_i != holdout}`` the mean cross entropy
+becomes ``(1/W) sum_train u_i CE_i``, ``W = sum_train u_i``, sigma the weighted sample
+std over the training rows, and the same read of the rows sums the held-out rows'
+weighted mean loss (``FitResult.holdout_log_loss``).  GPU:
+``csrc/kernels/fit_weighted.hip``; the weights are formed per tile, so another held-out
+fold costs one statistics pass and no copy -- :func:`cross_validate` chooses
+``reg_param`` that way.
+
 fp32 rows are converted to bf16, as :class:`psx.ops.score.Scorer` does: the fit sees
 the rounded features.
 
@@ -35,7 +45,7 @@ import torch
 
 from .. import _native
 from ..models.logreg import ModelSpec, to_reference_layout
-from ..models.reference import fit_reference
+from ..models.reference import fit_reference, weighted_feature_std, weighted_loss_grad
 from ..models.wide import WideSpec
 from ..utils.checkpoint import CKPT_NAME, FORMAT, _atomic_save
 from ..utils.data import Dataset
@@ -73,6 +83,7 @@ class FitResult:
     # a wide fit (psx/ops/wide_fit.py): ``spec`` is a WideSpec, ``features`` int32 [U] the sorted features the
     # training set touches and ``std`` their [U] sigmas (every other feature is excluded: sigma 0, coefficient 0)
     features: torch.Tensor | None = None
+    holdout_log_loss: float | None = None  # weighted mean loss of the held-out fold at ``w`` (FitWeights.holdout)
 
     def save(self, path_dir: str) -> str:
         """Write ``server.ckpt`` into ``path_dir`` (for ``Scorer.from_checkpoint`` /
@@ -126,6 +137,73 @@ def _check_data(spec: ModelSpec, ds, min_rows: int):
         raise ValueError(f"labels span [{lo}, {hi}], the model has classes [0, {spec.K})")
 
 
+@dataclass
+class FitWeights:
+    """Row weights of a dense fit: ``u_i = sample_weight_i * class_weight[y_i]``; rows
+    with ``fold_i == holdout`` are left out of the fit and scored separately.
+
+    Weighted calls in a row with the same dataset object reuse its resident copy, and
+    the device copies of ``sample_weight`` / ``fold`` are reused while the same tensor
+    OBJECTS are passed: do not change ``ds.X``, ``ds.y``, ``sample_weight`` or ``fold``
+    in place between such calls (pass new tensors instead) -- an edit is not seen."""
+    sample_weight: torch.Tensor | None = None  # [N], finite, >= 0
+    class_weight: torch.Tensor | str | None = None  # [K], or "balanced": N_train / (K_present * count_c)
+    fold: torch.Tensor | None = None  # [N] fold ids in 0..255
+    holdout: int | None = None
+
+
+class _Weights:
+    """``FitWeights`` checked against a dataset (ValueError before any launch): fp32
+    ``sw`` / ``cw`` and uint8 ``fold`` as the kernels read them (or None), and the
+    float64 effective training / held-out weights ``u`` / ``h`` of every row."""
+
+    def __init__(self, spec, ds, wts: FitWeights):
+        N, K = ds.rows, spec.K
+        y = ds.y.long().cpu()
+        self.src = wts
+        self.sw = self.cw = self.fold = None
+        self.holdout = -1
+        if wts.sample_weight is not None:
+            self.sw = wts.sample_weight.detach().to("cpu", torch.float32).reshape(-1)
+            if self.sw.numel() != N:
+                raise ValueError(f"{self.sw.numel()} sample weights for {N} rows")
+            if not bool(torch.isfinite(self.sw).all()) or bool((self.sw < 0).any()):
+                raise ValueError("sample weights must be finite and >= 0")
+        if wts.fold is not None:
+            f = wts.fold.detach().cpu().reshape(-1)
+            if f.numel() != N:
+                raise ValueError(f"{f.numel()} fold ids for {N} rows")
+            if f.is_floating_point() or int(f.min()) < 0 or int(f.max()) > 255:
+                raise ValueError("fold ids must be integers in [0, 255]")
+            self.fold = f.to(torch.uint8)
+        if wts.holdout is not None:
+            if self.fold is None or not 0 <= int(wts.holdout) <= 255:
+                raise ValueError("a held-out fold needs fold ids and a fold in [0, 255]")
+            self.holdout = int(wts.holdout)
+        held = self.fold == self.holdout if self.holdout >= 0 else torch.zeros(N, dtype=torch.bool)
+        cw = wts.class_weight
+        if isinstance(cw, str):
+            if cw != "balanced":
+                raise ValueError(f"class_weight is a [K] tensor or 'balanced', got {cw!r}")
+            cnt = torch.bincount(y[~held], minlength=K).double()
+            cw = torch.where(cnt > 0, float((~held).sum()) / (float((cnt > 0).sum()) * cnt.clamp_min(1)), cnt * 0)
+        if cw is not None:
+            self.cw = cw.detach().to("cpu", torch.float32).reshape(-1)
+            if self.cw.numel() != K:
+                raise ValueError(f"{self.cw.numel()} class weights for {K} classes")
+            if not bool(torch.isfinite(self.cw).all()) or bool((self.cw < 0).any()):
+                raise ValueError("class weights must be finite and >= 0")
+        v = torch.ones(N) if self.sw is None else self.sw
+        if self.cw is not None:
+            v = v * self.cw[y]  # the fp32 product the kernels form
+        v = v.double()
+        self.u, self.h = torch.where(held, v * 0, v), torch.where(held, v, v * 0)
+        if not float(self.u.sum()) > 1.0 or int((self.u > 0).sum()) < 2:
+            raise ValueError("the training rows need a weight sum > 1 and two rows of positive weight")
+        if self.holdout >= 0 and not float(self.h.sum()) > 0.0:
+            raise ValueError(f"the held-out fold {self.holdout} holds no weight")
+
+
 def _run_native(nat, st, w, check, valid_every, patience):
     """Drive a native fitter (begun) to its end, finalising the iterate into ``w``;
     with ``check`` the iterate is scored every ``valid_every`` accepted iterations.
@@ -177,6 +255,8 @@ class _Resident:
         n = ds.rows
         npad = (n + 31) // 32 * 32
         self.N, self.Npad = n, npad
+        self.wcache = {}  # padded device copies of a weighted call's sample weights / fold ids
+        self.applied = None  # the checked weights the native fitter holds for these rows
         if (npad == n and ds.X.device == device and ds.X.dtype == torch.bfloat16 and ds.X.is_contiguous()
                 and ds.y.device == device and ds.y.dtype == torch.int32 and ds.y.is_contiguous()):
             self.X, self.y = ds.X, ds.y  # already resident in the kernels' layout: no second copy
@@ -297,16 +377,103 @@ class BatchFitter(_FitterBase):
 
     _check_spec = staticmethod(_check_spec)
     _check_data = staticmethod(_check_data)
+    _wts: _Weights | None = None  # of the weighted call in progress
 
     def _new_native(self, hip):
         s = self.spec
         return hip.BatchFitter(s.K, s.F, s.Fp, self.opts.hist, self.opts.max_wg or 0)
 
     def _load(self, ds: Dataset) -> _Resident:
-        data = _Resident(ds, self.device)
-        self._native.set_data(data.X.data_ptr(), data.y.data_ptr(), data.N, data.Npad, stream_handle(self.device))
-        self._data = data  # the native fitter reads these buffers until the next set_data
+        wts, st = self._wts, stream_handle(self.device)
+        if wts is not None and self._data is not None and self._data.src is ds:
+            data = self._data  # weighted calls on one dataset object share its resident copy (cross_validate)
+        else:
+            data = _Resident(ds, self.device)
+            self._native.set_data(data.X.data_ptr(), data.y.data_ptr(), data.N, data.Npad, st)  # (clears the weights)
+            self._data = data  # the native fitter reads these buffers until the next set_data
+        if wts is not None and data.applied is not wts:
+            def padded(v, src, dtype):  # [Npad] on the device; one copy per source tensor
+                if v is None:
+                    return None
+                if data.wcache.get(dtype, (None, None))[0] is not src:
+                    t = torch.zeros(data.Npad, dtype=dtype, device=self.device)
+                    t[: data.N] = v.to(self.device)
+                    data.wcache[dtype] = (src, t)
+                return data.wcache[dtype][1]
+
+            sw = padded(wts.sw, wts.src.sample_weight, torch.float32)
+            fold = padded(wts.fold, wts.src.fold, torch.uint8)
+            self._native.set_weights(sw.data_ptr() if sw is not None else 0,
+                                     wts.cw.tolist() if wts.cw is not None else [],
+                                     fold.data_ptr() if fold is not None else 0, wts.holdout, st)
+            data.applied = wts
         return data
+
+    # ---- weighted calls ----------------------------------------------------------
+    def _weighted(self, ds, weights, min_rows):
+        self._check_data(self.spec, ds, min_rows)
+        return _Weights(self.spec, ds, weights)
+
+    def _rows64(self, ds):
+        return ds.X[:, : self.spec.F].to(torch.bfloat16).double().cpu(), ds.y.long().cpu()
+
+    def _eval_weighted(self, ds, w, wts):
+        """(training loss, gradient, held-out loss) of one raw evaluation under ``wts``."""
+        s = self.spec
+        if w.numel() != s.P:
+            raise ValueError(f"the model has {s.P} weights in device layout, got {w.numel()}")
+        if self._native is None:
+            X, y = self._rows64(ds)
+            wc = w.detach().double().cpu()
+            loss, gc, gb = weighted_loss_grad(X, y, s.coef(wc), s.intercept(wc), wts.u)
+            ho = weighted_loss_grad(X, y, s.coef(wc), s.intercept(wc), wts.h)[0]
+            return float(loss), s.pack(gc, gb, device=self.device), float(ho)
+        with torch.cuda.device(self.device):
+            self._wts = wts
+            try:
+                self._load(ds)
+            finally:
+                self._wts = None
+            st = stream_handle(self.device)
+            wd = w.detach().to(self.device, torch.float32).reshape(-1).contiguous()
+            g = torch.empty(s.P, dtype=torch.float32, device=self.device)
+            loss = self._native.loss_grad(wd.data_ptr(), g.data_ptr(), st)
+            return float(loss), g, float(self._native.holdout_loss(st))
+
+    def loss_grad(self, ds, w: torch.Tensor, weights: FitWeights | None = None):
+        """As :meth:`_FitterBase.loss_grad`; with ``weights`` the weighted mean loss of the
+        training rows and its gradient."""
+        if weights is None:
+            if self._native is not None and self._native.weighted:  # the resident rows keep their statistics pass
+                with torch.cuda.device(self.device):
+                    self._native.set_weights(stream=stream_handle(self.device))
+                if self._data is not None:
+                    self._data.applied = None
+            return super().loss_grad(ds, w)
+        return self._eval_weighted(ds, w, self._weighted(ds, weights, 1))[:2]
+
+    def holdout_loss(self, ds, w: torch.Tensor, weights: FitWeights) -> float:
+        """The held-out fold's weighted mean loss at ``w``: one raw evaluation."""
+        wts = self._weighted(ds, weights, 1)
+        if wts.holdout < 0:
+            raise ValueError("holdout_loss needs FitWeights.holdout")
+        return self._eval_weighted(ds, w, wts)[2]
+
+    def fit(self, train, w0: torch.Tensor | None = None, valid=None, valid_every: int = 1,
+            patience: int | None = None, weights: FitWeights | None = None) -> FitResult:
+        """As :meth:`_FitterBase.fit`; with ``weights`` the weighted objective, and
+        ``holdout_log_loss`` from one raw evaluation at the returned weights."""
+        if weights is None:
+            return super().fit(train, w0, valid, valid_every, patience)
+        wts = self._weighted(train, weights, 2)
+        self._wts = wts
+        try:
+            res = super().fit(train, w0, valid, valid_every, patience)
+        finally:
+            self._wts = None
+        if wts.holdout >= 0:
+            res.holdout_log_loss = self._eval_weighted(train, res.w, wts)[2]
+        return res
 
     def _result_vector(self, w0):
         return torch.empty(self.spec.P, dtype=torch.float32, device=self.device)  # finalize writes all of it
@@ -327,8 +494,11 @@ class BatchFitter(_FitterBase):
 
     def _fit_cpu(self, train, w0, valid, valid_every, patience) -> FitResult:
         s, o = self.spec, self.opts
-        X = train.X[:, : s.F].to(torch.bfloat16).double().cpu()
-        y = train.y.long().cpu()
+        X, y = self._rows64(train)
+        extra = {}
+        if self._wts is not None:  # float64 weighted closures through the oracle's own hooks
+            u = self._wts.u
+            extra = dict(loss_grad=lambda ce, bb: weighted_loss_grad(X, y, ce, bb, u), std=weighted_feature_std(X, u))
         c0 = b0 = None
         if w0 is not None:
             wc = w0.detach().float().cpu().reshape(-1)
@@ -336,7 +506,7 @@ class BatchFitter(_FitterBase):
 
         def run(max_iter):
             return fit_reference(X, y, c0, b0, num_classes=s.K, reg_param=o.reg_param, max_iter=max_iter, tol=o.tol,
-                                 hist=o.hist, ls_max=o.ls_max, zero_const=o.zero_const)
+                                 hist=o.hist, ls_max=o.ls_max, zero_const=o.zero_const, **extra)
 
         t0 = time.perf_counter()
         ref = run(o.max_iter)
@@ -357,4 +527,42 @@ def loss_grad(spec: ModelSpec, ds: Dataset, w: torch.Tensor, device, max_wg: int
     return BatchFitter(spec, device, FitOptions(max_wg=max_wg)).loss_grad(ds, w)
 
 
-__all__ = ["BatchFitter", "FitOptions", "FitResult", "loss_grad"]
+@dataclass
+class CVResult:
+    reg_params: list
+    losses: list  # [R][folds] held-out weighted mean loss
+    means: list  # [R]
+    best_reg_param: float
+    fold: torch.Tensor  # [N] uint8, the fold of every row
+    seconds: float
+
+
+def cross_validate(spec: ModelSpec, ds: Dataset, reg_params, folds: int = 5, seed: int = 0, device="cpu",
+                   opts: FitOptions | None = None, sample_weight=None, class_weight=None) -> CVResult:
+    """K-fold choice of ``reg_param``: fold ids are drawn once, the rows are made resident
+    once, and the ``folds * len(reg_params)`` fits differ only in the held-out fold (one
+    statistics pass, no copy) and the penalty.  The best penalty has the lowest mean
+    held-out loss (the first of equals).  ``ds`` and ``sample_weight`` must not change
+    while it runs: every fit reuses the first one's resident copies (see :class:`FitWeights`)."""
+    regs = [float(r) for r in reg_params]
+    if not regs or not 2 <= folds <= 255 or folds > ds.rows:
+        raise ValueError("cross_validate needs penalties and 2 <= folds <= min(255, rows)")
+    t0 = time.perf_counter()
+    g = torch.Generator().manual_seed(seed)
+    fold = (torch.randperm(ds.rows, generator=g) % folds).to(torch.uint8)
+    o = opts or FitOptions()
+    if is_gpu(torch.device(device)):
+        ds = ds.to(device)
+    f = BatchFitter(spec, device, o)
+    losses = []
+    for r in regs:
+        f.opts = FitOptions(**{**asdict(o), "reg_param": r})
+        _check_options(f.opts)
+        # (every fit is handed the same dataset object: its first load is the only copy)
+        losses.append([f.fit(ds, weights=FitWeights(sample_weight, class_weight, fold, k)).holdout_log_loss
+                       for k in range(folds)])
+    means = [sum(row) / folds for row in losses]
+    return CVResult(regs, losses, means, regs[means.index(min(means))], fold, time.perf_counter() - t0)
+
+
+__all__ = ["BatchFitter", "CVResult", "FitOptions", "FitResult", "FitWeights", "cross_validate", "loss_grad"]

@@ -6,12 +6,17 @@
            solve time / evaluations and as the slope between a 1-slot and a 9-slot solve
            (which takes the solve's statistics pass out).  One process, device events,
            one warm-up, three repeats, the variants alternating inside every repeat.
+  eval --weighted   the plain evaluation against the weighted one (sample weights, a
+           class table, 5 folds with one held out: csrc/kernels/fit_weighted.hip) on
+           the same rows, alternating, 9 repeats; then one ``cross_validate`` run of
+           5 folds x 4 penalties on them and the time of one fold switch (the
+           weighted statistics pass).
   truth    BASELINE.md's ground-truth row: fit the 90k-row synthetic fine-food set with
            default options, score the 4,877-row test set.
   ceiling  a fit of --ceiling_rows x 1,024 rows drawn on the device from a planted
            softmax model (a size whose float64 copy no host holds).
 
-Usage: python tools/bench_fit.py [--what eval,truth,ceiling] [--rows N] [--ceiling_rows N] [--out FILE.json]
+Usage: python tools/bench_fit.py [--what eval,truth,ceiling] [--weighted] [--rows N] [--ceiling_rows N] [--out FILE.json]
 """
 from __future__ import annotations
 
@@ -28,7 +33,7 @@ if ROOT not in sys.path:
     sys.path.insert(0, ROOT)
 
 from psx.models.logreg import ModelSpec  # noqa: E402
-from psx.ops.fit import BatchFitter  # noqa: E402
+from psx.ops.fit import BatchFitter, FitOptions, FitWeights, cross_validate  # noqa: E402
 from psx.ops.lr import LocalSolveOp, SolverOptions  # noqa: E402
 from psx.ops.score import Scorer  # noqa: E402
 from psx.runtime.buffer import DeviceRing  # noqa: E402
@@ -111,6 +116,38 @@ def bench_eval(dev, rows: int, F: int = 1024, K: int = 6) -> dict:
     return out
 
 
+def bench_weighted(dev, rows: int, F: int = 1024, K: int = 6) -> dict:
+    spec = ModelSpec(F, K)
+    ds, _ = planted(dev, rows, spec.Fp, K, seed=0)
+    w = spec.init("random", seed=1, scale=0.05).to(dev)
+    g = torch.Generator().manual_seed(0)
+    wts = FitWeights(torch.rand(rows, generator=g) * 2, 0.5 + torch.rand(K, generator=g),
+                     (torch.randperm(rows, generator=g) % 5).to(torch.uint8), 0)
+    plain, weighted = BatchFitter(spec, dev), BatchFitter(spec, dev)
+    plain.loss_grad(ds, w)
+    weighted.loss_grad(ds, w, weights=wts)  # both hold the rows now; the native calls below skip the host checks
+    st = torch.cuda.current_stream(dev).cuda_stream
+    assert rows % 32 == 0  # the native call reads [Npad] streams
+    sw, fold = wts.sample_weight.to(dev), wts.fold.to(dev)
+    cw, gbuf = wts.class_weight.tolist(), torch.empty(spec.P, device=dev)
+    ms = _time({"plain_eval": lambda: plain._native.loss_grad(w.data_ptr(), gbuf.data_ptr(), st),
+                "weighted_eval": lambda: weighted._native.loss_grad(w.data_ptr(), gbuf.data_ptr(), st),
+                "fold_switch": lambda: weighted._native.set_weights(sw.data_ptr(), cw, fold.data_ptr(), 1, st)},
+               repeats=9)
+    out = {"rows": rows, "ms": ms}
+    nbytes = rows * spec.Fp * 2
+    for k, v in ms.items():
+        lo, med, hi = _mmm(v)
+        print(f"{k:14s} ms min/med/max {lo:8.3f} {med:8.3f} {hi:8.3f}   {nbytes / med / 1e9:6.3f} TB/s of rows")
+    t0 = time.perf_counter()
+    cv = cross_validate(spec, ds, [1e-4, 1e-3, 1e-2, 1e-1], folds=5, device=dev, opts=FitOptions(max_iter=20))
+    torch.cuda.synchronize()
+    out["cv"] = {"seconds": time.perf_counter() - t0, "means": cv.means, "best_reg_param": cv.best_reg_param}
+    print(f"cross_validate 5 folds x 4 penalties (max_iter 20): {out['cv']['seconds']:.3f} s, means {cv.means}, "
+          f"best {cv.best_reg_param}")
+    return out
+
+
 def _fit_report(name, res, extra=None):
     ev = res.evals
     line = {"case": name, "seconds": res.seconds, "iters": res.iters, "evals": ev, "reason": res.reason,
@@ -156,6 +193,7 @@ def bench_ceiling(dev, rows: int, F: int = 1024, K: int = 6) -> dict:
 def main(argv=None) -> int:
     ap = argparse.ArgumentParser()
     ap.add_argument("--what", default="eval,truth")
+    ap.add_argument("--weighted", action="store_true", help="eval: the plain against the weighted evaluation, and CV")
     ap.add_argument("--rows", type=int, default=1 << 20)
     ap.add_argument("--ceiling_rows", type=int, default=1 << 24)
     ap.add_argument("--out", default=None, help="also write the results as JSON")
@@ -167,7 +205,7 @@ def main(argv=None) -> int:
     res = {}
     for what in a.what.split(","):
         if what == "eval":
-            res[what] = bench_eval(dev, a.rows)
+            res[what] = bench_weighted(dev, a.rows) if a.weighted else bench_eval(dev, a.rows)
         elif what == "truth":
             res[what] = bench_truth(dev)
         elif what == "ceiling":
