@@ -448,6 +448,21 @@ PYBIND11_MODULE(_psx_hip, m) {
           [](WideBatchFitter& f, uintptr_t out, uintptr_t stream) { f.read_std(P<float>(out), S(stream)); },
           py::arg("out"), py::arg("stream") = 0)
       .def(
+          "set_weights",
+          [](WideBatchFitter& f, uintptr_t sample_weight, const std::vector<float>& class_weight, uintptr_t fold,
+             int holdout, uintptr_t stream) {
+            if (!class_weight.empty() && (int)class_weight.size() != f.class_weights())
+              throw std::invalid_argument("set_weights: one class weight per class (two for the one-logit model)");
+            f.set_weights(P<const float>(sample_weight), class_weight.empty() ? nullptr : class_weight.data(),
+                          P<const uint8_t>(fold), holdout, S(stream));
+          },
+          py::arg("sample_weight") = 0, py::arg("class_weight") = std::vector<float>{}, py::arg("fold") = 0,
+          py::arg("holdout") = -1, py::arg("stream") = 0)
+      .def_property_readonly("weighted", &WideBatchFitter::weighted)
+      .def(
+          "holdout_loss", [](WideBatchFitter& f, uintptr_t stream) { return f.holdout_loss(S(stream)); },
+          py::arg("stream") = 0)
+      .def(
           "stage_ms",
           [](WideBatchFitter& f, bool raw, uintptr_t stream) {
             py::gil_scoped_release nogil;

@@ -85,7 +85,7 @@ def _local_includes(src):
 # verified with.  The arithmetic is the same IEEE fp32 either way; only the compiler's
 # choice between fused and unfused forms can differ (see fit_reduce_w_kernel).
 NO_PACKED_FP32 = ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"]
-EXTRA_CFLAGS = {"fit_weighted.hip": NO_PACKED_FP32}
+EXTRA_CFLAGS = {"fit_weighted.hip": NO_PACKED_FP32, "wide_fit_weighted.hip": NO_PACKED_FP32}
 
 
 def _compile_link(compiler, sources, out, cflags, ldflags, jobs, objdir, headers=()):

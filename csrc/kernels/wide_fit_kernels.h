@@ -63,6 +63,8 @@ void launch_wide_fit_begin(const WideFitDev& dv, const float* w0, int zero_const
 void launch_wide_fit_rows(const WideFitDev& dv, int G, hipStream_t s);
 void launch_wide_fit_cols(const WideFitDev& dv, hipStream_t s);
 int wide_fit_reduce_grid(int n);  // workgroups of the reduction = rows of dpart
+// the W per-wave residual sums -> bsum (the first launch of launch_wide_fit_reduce, also of the weighted one)
+void launch_wide_fit_bsum(const WideFitDev& dv, hipStream_t s);
 void launch_wide_fit_reduce(const WideFitDev& dv, double reg, int raw, hipStream_t s);
 void launch_wide_fit_update(const WideFitDev& dv, const FitStep& st, hipStream_t s);
 // w_out [F*KP + KP] (already holding the untouched features' values) gets the touched

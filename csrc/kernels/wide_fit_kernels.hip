@@ -398,9 +398,11 @@ void launch_wide_fit_cols(const WideFitDev& dv, hipStream_t s) {
 
 int wide_fit_reduce_grid(int n) { return (int)blocks_of(n, 256, kWideReduceMaxWG); }
 
+void launch_wide_fit_bsum(const WideFitDev& dv, hipStream_t s) { wide_fit_bsum_kernel<<<1, 256, 0, s>>>(dv); }
+
 void launch_wide_fit_reduce(const WideFitDev& dv, double reg, int raw, hipStream_t s) {
   const int NB = wide_fit_reduce_grid(dv.n);
-  wide_fit_bsum_kernel<<<1, 256, 0, s>>>(dv);
+  launch_wide_fit_bsum(dv, s);
   wide_fit_reduce_kernel<<<NB, 256, 0, s>>>(dv, reg, raw);
   wide_fit_dots_kernel<<<1, 256, 0, s>>>(dv, NB, reg, raw);
 }

@@ -16,6 +16,7 @@
 #include <vector>
 
 #include "../kernels/wide_fit_kernels.h"
+#include "../kernels/wide_fit_weighted.h"
 #include "fit_driver.h"
 
 namespace psx {
@@ -28,6 +29,20 @@ class WideBatchFitter : public FitDriver {
 
   void set_data(const WideFitData& d, hipStream_t s);
   void read_std(float* std_out, hipStream_t s);  // [U]
+  // Row weights u_i = sample_weight_i * class_weight[y_i] and a held-out fold (the
+  // objective is stated in csrc/kernels/wide_fit_weighted.h), with BatchFitter's
+  // contract: sample_weight [N] fp32 and fold [N] uint8 are device buffers, caller-owned
+  // as the rows are; class_weight is K host floats (two, for labels 0 and 1, when
+  // K == 1); each may be null.  holdout < 0: no row is held out.  Valid after set_data;
+  // ends a fit in progress and runs the weights and statistics kernels -- the inverted
+  // index and the work items are untouched.  All null and holdout < 0: back to the plain
+  // kernels and statistics.  A new set_data clears the weights.
+  void set_weights(const float* sample_weight, const float* class_weight, const uint8_t* fold, int holdout,
+                   hipStream_t s);
+  bool weighted() const { return weighted_; }
+  int class_weights() const { return dv_.K == 1 ? 2 : dv_.K; }  // entries of the class table
+  // The held-out rows' weighted mean loss at the last evaluation (0 without held-out weight).
+  double holdout_loss(hipStream_t s);
   // Device-event milliseconds of one evaluation at the current trial point, by stage:
   // row pass, column pass, reduction (tools/bench_wide_fit.py).  raw = 1: the reduction
   // of loss_grad (gradient only); raw = 0: the reduction of a fit's evaluation, which
@@ -47,7 +62,11 @@ class WideBatchFitter : public FitDriver {
   void export_grad(float* grad, hipStream_t s) override;
 
  private:
+  void launch_rows(hipStream_t s);                         // the plain or the weighted row pass
+  void launch_reduce(double reg, int raw, hipStream_t s);  // ... and reduction
   WideFitDev dv_{};
+  WideFitWeightsDev wd_{};
+  bool weighted_ = false;
   void* ws_ = nullptr;  // per-dataset workspace (every size depends on U, N or the items)
 };
 

@@ -34,6 +34,9 @@ void WideBatchFitter::set_data(const WideFitData& d, hipStream_t s) {
       (d.n_short > 0 && !d.short_items) || (d.n_long > 0 && !d.long_items))
     throw std::invalid_argument("null dataset pointer");
   end_fit();
+  weighted_ = false;
+  wd_ = WideFitWeightsDev{};
+  wd_.holdout = -1;
   if (ws_) {
     hip_check(hipStreamSynchronize(s), "hipStreamSynchronize");
     hip_check(hipFree(ws_), "hipFree(wide fit workspace)");
@@ -56,6 +59,8 @@ void WideBatchFitter::set_data(const WideFitData& d, hipStream_t s) {
     c.take(dv_.weff, (size_t)dv_.nv), c.take(dv_.std_, U1), c.take(dv_.inv_std, U1);
     c.take(dv_.R, (size_t)d.N * KP), c.take(dv_.gitem, ((size_t)d.n_items + 1) * KP);
     c.take(dv_.part, (size_t)dv_.W * 32), c.take(dv_.bsum, 16);
+    c.take(wd_.ueff, (size_t)d.N), c.take(wd_.wpart, (size_t)wide_fit_weights_grid(d.N) * 3);
+    c.take(wd_.wsum, 3), c.take(wd_.ho, 1);
   };
   Carver size;
   layout(size);
@@ -67,6 +72,53 @@ void WideBatchFitter::set_data(const WideFitData& d, hipStream_t s) {
   hip_check(hipGetLastError(), "wide_fit_stats launch");
 }
 
+void WideBatchFitter::set_weights(const float* sample_weight, const float* class_weight, const uint8_t* fold,
+                                  int holdout, hipStream_t s) {
+  if (!ws_) throw std::runtime_error("set_weights: no dataset (set_data first)");
+  if (holdout > 255) throw std::invalid_argument("set_weights: fold ids are 0..255");
+  if (holdout >= 0 && !fold) throw std::invalid_argument("set_weights: a held-out fold needs fold ids");
+  end_fit();
+  if (!sample_weight && !class_weight && holdout < 0) {
+    if (weighted_) {  // sigma is the weighted one: the plain statistics again
+      launch_wide_fit_stats(dv_, s);
+      hip_check(hipGetLastError(), "wide_fit_stats launch");
+    }
+    weighted_ = false;
+    return;
+  }
+  wd_.sw = sample_weight;
+  wd_.fold = fold;
+  wd_.holdout = holdout < 0 ? -1 : holdout;
+  const int nc = class_weights();
+  for (int c = 0; c < 16; ++c) wd_.cw[c] = c < nc ? (class_weight ? class_weight[c] : 1.f) : 0.f;
+  weighted_ = true;
+  launch_wide_fit_weights(dv_, wd_, s);
+  launch_wide_fit_stats_w(dv_, wd_, s);
+  hip_check(hipGetLastError(), "wide_fit_stats_w launch");
+}
+
+double WideBatchFitter::holdout_loss(hipStream_t s) {
+  if (!weighted_) throw std::runtime_error("holdout_loss: no weights (set_weights first)");
+  double v = 0.0;
+  hip_check(hipMemcpyAsync(&v, wd_.ho, sizeof(double), hipMemcpyDeviceToHost, s), "hipMemcpyAsync(held-out loss)");
+  hip_check(hipStreamSynchronize(s), "hipStreamSynchronize(held-out loss)");
+  return v;
+}
+
+void WideBatchFitter::launch_rows(hipStream_t s) {
+  if (weighted_)
+    launch_wide_fit_rows_w(dv_, wd_, G_, s);
+  else
+    launch_wide_fit_rows(dv_, G_, s);
+}
+
+void WideBatchFitter::launch_reduce(double reg, int raw, hipStream_t s) {
+  if (weighted_)
+    launch_wide_fit_reduce_w(dv_, wd_, reg, raw, s);
+  else
+    launch_wide_fit_reduce(dv_, reg, raw, s);
+}
+
 FitVectors WideBatchFitter::vectors() const {
   return {dv_.n, dv_.nv, dv_.H, dv_.x, dv_.d, dv_.g_c, dv_.g_t, dv_.beta_t, dv_.S, dv_.Y, dv_.wfix, dv_.out};
 }
@@ -76,9 +128,9 @@ void WideBatchFitter::launch_begin(const float* w0, int zero_const, int raw, hip
 }
 
 void WideBatchFitter::launch_eval(double reg, int raw, hipStream_t s) {
-  launch_wide_fit_rows(dv_, G_, s);
+  launch_rows(s);
   launch_wide_fit_cols(dv_, s);
-  launch_wide_fit_reduce(dv_, reg, raw, s);
+  launch_reduce(reg, raw, s);
 }
 
 void WideBatchFitter::launch_update(const FitStep& st, hipStream_t s) { launch_wide_fit_update(dv_, st, s); }
@@ -111,11 +163,11 @@ std::vector<float> WideBatchFitter::stage_ms(int raw, hipStream_t s) {
   if (!ws_) throw std::runtime_error("stage_ms: no dataset (set_data first)");
   StageEvents t;
   hip_check(hipEventRecord(t.ev[0], s), "hipEventRecord");
-  launch_wide_fit_rows(dv_, G_, s);
+  launch_rows(s);
   hip_check(hipEventRecord(t.ev[1], s), "hipEventRecord");
   launch_wide_fit_cols(dv_, s);
   hip_check(hipEventRecord(t.ev[2], s), "hipEventRecord");
-  launch_wide_fit_reduce(dv_, 0.0, raw, s);
+  launch_reduce(0.0, raw, s);
   hip_check(hipEventRecord(t.ev[3], s), "hipEventRecord");
   hip_check(hipEventSynchronize(t.ev[3]), "hipEventSynchronize");
   std::vector<float> ms(3);

@@ -11,8 +11,8 @@ CSVs and binary row caches fit the dense model.  A LIBSVM file (``.svm``, ``.lib
 largest training id + 1); ``--sigmoid`` selects the one-logit model with labels {0, 1},
 ``--zero_based`` files whose feature ids start at 0.  ``--valid`` / ``--valid_frac`` score
 the iterates on held-out rows and keep the best one (``--patience N`` stops after N checks
-without improvement).  Dense model only: ``--class_weight`` weighs the rows by their class
-(``balanced``: N / (classes present * class count)); ``--cv K --reg_params a,b,c`` runs a
+without improvement).  ``--class_weight`` weighs the rows by their class (``balanced``:
+N / (classes present * class count); with ``--sigmoid`` two weights, ``w0,w1``); ``--cv K --reg_params a,b,c`` runs a
 K-fold cross-validation of the penalties on the resident rows, prints its table to stderr
 and fits the whole set at the best one (it excludes ``--valid`` / ``--valid_frac``).
 ``--checkpoint_dir`` gets a ``server.ckpt`` that
@@ -53,8 +53,8 @@ def fit_parser():
     ap.add_argument("--num_features", type=int, default=None, help="wide model: F (default: largest training id + 1)")
     ap.add_argument("--sigmoid", action="store_true", help="wide model: one logit, labels {0, 1}")
     ap.add_argument("--zero_based", action="store_true", help="LIBSVM feature ids start at 0")
-    ap.add_argument("--class_weight", default=None, help="dense model: 'balanced' or one weight per class, w0,w1,...")
-    ap.add_argument("--cv", type=int, default=0, help="dense model: folds of a cross-validation over --reg_params")
+    ap.add_argument("--class_weight", default=None, help="'balanced' or one weight per class, w0,w1,... (--sigmoid: w0,w1)")
+    ap.add_argument("--cv", type=int, default=0, help="folds of a cross-validation over --reg_params")
     ap.add_argument("--reg_params", default=None, help="penalties --cv compares, a,b,c")
     return ap
 
@@ -94,8 +94,6 @@ def main(argv=None) -> int:
     wide = data_mod.is_libsvm_path(a.train)
     if not wide and (a.num_features is not None or a.sigmoid or a.zero_based):
         ap.error("--num_features, --sigmoid and --zero_based go with a LIBSVM --train file (the wide model)")
-    if wide and (a.class_weight or a.cv):
-        ap.error("--class_weight and --cv go with the dense model")
     num_features = a.num_features
 
     def load(path):

@@ -82,15 +82,22 @@ def weighted_feature_std(X, u):
 
 def weighted_loss_grad(X, y, coef_eff, b, u):
     """``multinomial_loss_grad`` with row weights: ``(1/W) sum u CE`` and its gradients,
-    ``W = sum u`` (0 for all of them when W is 0)."""
+    ``W = sum u`` (0 for all of them when W is 0).  One coefficient row (K == 1) is the
+    binary sigmoid model with labels {0, 1}."""
     u = u.to(X.dtype)
     W = u.sum()
     if float(W) == 0.0:
         return torch.zeros((), dtype=X.dtype), torch.zeros_like(coef_eff), torch.zeros_like(b)
     z = X @ coef_eff.t() + b
-    ce = torch.logsumexp(z, dim=1) - z.gather(1, y.view(-1, 1)).squeeze(1)
-    r = torch.softmax(z, dim=1)
-    r[torch.arange(X.shape[0]), y] -= 1.0
+    if coef_eff.shape[0] == 1:
+        zz = z[:, 0]
+        yy = (y > 0).to(z.dtype)
+        ce = torch.nn.functional.softplus(zz) - yy * zz
+        r = (torch.sigmoid(zz) - yy).view(-1, 1)
+    else:
+        ce = torch.logsumexp(z, dim=1) - z.gather(1, y.view(-1, 1)).squeeze(1)
+        r = torch.softmax(z, dim=1)
+        r[torch.arange(X.shape[0]), y] -= 1.0
     r = r * u.view(-1, 1)
     return (u * ce).sum() / W, (r.t() @ X) / W, r.sum(0) / W
 

@@ -139,13 +139,14 @@ def _check_data(spec: ModelSpec, ds, min_rows: int):
 
 @dataclass
 class FitWeights:
-    """Row weights of a dense fit: ``u_i = sample_weight_i * class_weight[y_i]``; rows
+    """Row weights of a fit: ``u_i = sample_weight_i * class_weight[y_i]``; rows
     with ``fold_i == holdout`` are left out of the fit and scored separately.
 
     Weighted calls in a row with the same dataset object reuse its resident copy, and
     the device copies of ``sample_weight`` / ``fold`` are reused while the same tensor
     OBJECTS are passed: do not change ``ds.X``, ``ds.y``, ``sample_weight`` or ``fold``
-    in place between such calls (pass new tensors instead) -- an edit is not seen."""
+    in place between such calls (pass new tensors instead) -- an edit is not seen.
+    The one-logit wide model (``K == 1``) has a two-entry class table, labels 0 and 1."""
     sample_weight: torch.Tensor | None = None  # [N], finite, >= 0
     class_weight: torch.Tensor | str | None = None  # [K], or "balanced": N_train / (K_present * count_c)
     fold: torch.Tensor | None = None  # [N] fold ids in 0..255
@@ -158,7 +159,7 @@ class _Weights:
     float64 effective training / held-out weights ``u`` / ``h`` of every row."""
 
     def __init__(self, spec, ds, wts: FitWeights):
-        N, K = ds.rows, spec.K
+        N, K = ds.rows, max(2, spec.K)  # (the one-logit model has labels 0 and 1)
         y = ds.y.long().cpu()
         self.src = wts
         self.sw = self.cw = self.fold = None
@@ -272,7 +273,10 @@ class _FitterBase:
     resident dataset, :meth:`fit`, :meth:`loss_grad` and the GPU path of both.  A
     subclass supplies ``_check_spec`` / ``_check_data``, ``_new_native``, ``_load``,
     ``_result_vector``, ``_std_features`` and its CPU paths (``_fit_cpu``,
-    ``_loss_grad_cpu``)."""
+    ``_loss_grad_cpu``, ``_eval_weighted_cpu``).  The resident dataset a ``_load`` returns
+    has ``src``, ``N``, ``Npad`` (the length of the weight streams), ``wcache`` and ``applied``."""
+
+    _wts: _Weights | None = None  # of the weighted call in progress
 
     def __init__(self, spec, device, opts: FitOptions | None = None):
         self._check_spec(spec)
@@ -286,13 +290,70 @@ class _FitterBase:
                 self._native = self._new_native(_native.hip())
         self._data = None
 
+    # ---- weights -------------------------------------------------------------
+    def _weighted(self, ds, weights, min_rows):
+        self._check_data(self.spec, ds, min_rows)
+        return _Weights(self.spec, ds, weights)
+
+    def _apply_weights(self, data, wts):
+        """Hand ``wts`` to the native fitter for the resident ``data`` (a statistics pass, no copy of the rows)."""
+        def padded(v, src, dtype):  # [Npad] on the device; one copy per source tensor
+            if v is None:
+                return None
+            if data.wcache.get(dtype, (None, None))[0] is not src:
+                t = torch.zeros(data.Npad, dtype=dtype, device=self.device)
+                t[: data.N] = v.to(self.device)
+                data.wcache[dtype] = (src, t)
+            return data.wcache[dtype][1]
+
+        sw = padded(wts.sw, wts.src.sample_weight, torch.float32)
+        fold = padded(wts.fold, wts.src.fold, torch.uint8)
+        self._native.set_weights(sw.data_ptr() if sw is not None else 0,
+                                 wts.cw.tolist() if wts.cw is not None else [],
+                                 fold.data_ptr() if fold is not None else 0, wts.holdout, stream_handle(self.device))
+        data.applied = wts
+
+    def _eval_weighted(self, ds, w, wts):
+        """(training loss, gradient, held-out loss) of one raw evaluation under ``wts``."""
+        s = self.spec
+        if w.numel() != s.P:
+            raise ValueError(f"the model has {s.P} weights in device layout, got {w.numel()}")
+        self._wts = wts
+        try:
+            if self._native is None:
+                return self._eval_weighted_cpu(ds, w, wts)
+            with torch.cuda.device(self.device):
+                self._load(ds)
+                st = stream_handle(self.device)
+                wd = w.detach().to(self.device, torch.float32).reshape(-1).contiguous()
+                g = torch.empty(s.P, dtype=torch.float32, device=self.device)
+                loss = self._native.loss_grad(wd.data_ptr(), g.data_ptr(), st)
+                return float(loss), g, float(self._native.holdout_loss(st))
+        finally:
+            self._wts = None
+
+    def holdout_loss(self, ds, w: torch.Tensor, weights: FitWeights) -> float:
+        """The held-out fold's weighted mean loss at ``w``: one raw evaluation."""
+        wts = self._weighted(ds, weights, 1)
+        if wts.holdout < 0:
+            raise ValueError("holdout_loss needs FitWeights.holdout")
+        return self._eval_weighted(ds, w, wts)[2]
+
     # ---- one evaluation ------------------------------------------------------
-    def loss_grad(self, ds, w: torch.Tensor):
+    def loss_grad(self, ds, w: torch.Tensor, weights: FitWeights | None = None):
         """Mean loss of ``w`` (device layout ``[P]``) over ``ds`` and its gradient in
         the same layout (zero for every feature a sparse ``ds`` does not touch):
         original feature space, no standardisation, no penalty.  Calls in a row with
         the same ``ds`` object reuse its resident copy (and skip the checks): do not
-        change its tensors in between."""
+        change its tensors in between.  With ``weights`` the weighted mean loss of the
+        training rows and its gradient."""
+        if weights is not None:
+            return self._eval_weighted(ds, w, self._weighted(ds, weights, 1))[:2]
+        if self._native is not None and self._native.weighted:  # the resident rows keep their statistics pass
+            with torch.cuda.device(self.device):
+                self._native.set_weights(stream=stream_handle(self.device))
+            if self._data is not None:
+                self._data.applied = None
         s = self.spec
         resident = self._data is not None and self._data.src is ds
         if not resident:
@@ -311,13 +372,25 @@ class _FitterBase:
 
     # ---- the fit ---------------------------------------------------------------
     def fit(self, train, w0: torch.Tensor | None = None, valid=None, valid_every: int = 1,
-            patience: int | None = None) -> FitResult:
+            patience: int | None = None, weights: FitWeights | None = None) -> FitResult:
         """Fit ``train`` from zeros or from ``w0`` (device layout, a warm start).
 
         With ``valid`` the current iterate is scored with :class:`Scorer` every
         ``valid_every`` accepted iterations; the result carries the iterate with the
         lowest validation log-loss, and ``patience`` checks in a row without
-        improvement end the fit with reason ``early_stop``."""
+        improvement end the fit with reason ``early_stop``.  With ``weights`` the
+        weighted objective, and ``holdout_log_loss`` from one raw evaluation at the
+        returned weights."""
+        if weights is not None:
+            wts = self._weighted(train, weights, 2)
+            self._wts = wts
+            try:
+                res = self.fit(train, w0, valid, valid_every, patience)
+            finally:
+                self._wts = None
+            if wts.holdout >= 0:
+                res.holdout_log_loss = self._eval_weighted(train, res.w, wts)[2]
+            return res
         s = self.spec
         self._check_data(s, train, 2)
         if valid is not None:
@@ -377,8 +450,6 @@ class BatchFitter(_FitterBase):
 
     _check_spec = staticmethod(_check_spec)
     _check_data = staticmethod(_check_data)
-    _wts: _Weights | None = None  # of the weighted call in progress
-
     def _new_native(self, hip):
         s = self.spec
         return hip.BatchFitter(s.K, s.F, s.Fp, self.opts.hist, self.opts.max_wg or 0)
@@ -392,88 +463,19 @@ class BatchFitter(_FitterBase):
             self._native.set_data(data.X.data_ptr(), data.y.data_ptr(), data.N, data.Npad, st)  # (clears the weights)
             self._data = data  # the native fitter reads these buffers until the next set_data
         if wts is not None and data.applied is not wts:
-            def padded(v, src, dtype):  # [Npad] on the device; one copy per source tensor
-                if v is None:
-                    return None
-                if data.wcache.get(dtype, (None, None))[0] is not src:
-                    t = torch.zeros(data.Npad, dtype=dtype, device=self.device)
-                    t[: data.N] = v.to(self.device)
-                    data.wcache[dtype] = (src, t)
-                return data.wcache[dtype][1]
-
-            sw = padded(wts.sw, wts.src.sample_weight, torch.float32)
-            fold = padded(wts.fold, wts.src.fold, torch.uint8)
-            self._native.set_weights(sw.data_ptr() if sw is not None else 0,
-                                     wts.cw.tolist() if wts.cw is not None else [],
-                                     fold.data_ptr() if fold is not None else 0, wts.holdout, st)
-            data.applied = wts
+            self._apply_weights(data, wts)
         return data
-
-    # ---- weighted calls ----------------------------------------------------------
-    def _weighted(self, ds, weights, min_rows):
-        self._check_data(self.spec, ds, min_rows)
-        return _Weights(self.spec, ds, weights)
 
     def _rows64(self, ds):
         return ds.X[:, : self.spec.F].to(torch.bfloat16).double().cpu(), ds.y.long().cpu()
 
-    def _eval_weighted(self, ds, w, wts):
-        """(training loss, gradient, held-out loss) of one raw evaluation under ``wts``."""
+    def _eval_weighted_cpu(self, ds, w, wts):
         s = self.spec
-        if w.numel() != s.P:
-            raise ValueError(f"the model has {s.P} weights in device layout, got {w.numel()}")
-        if self._native is None:
-            X, y = self._rows64(ds)
-            wc = w.detach().double().cpu()
-            loss, gc, gb = weighted_loss_grad(X, y, s.coef(wc), s.intercept(wc), wts.u)
-            ho = weighted_loss_grad(X, y, s.coef(wc), s.intercept(wc), wts.h)[0]
-            return float(loss), s.pack(gc, gb, device=self.device), float(ho)
-        with torch.cuda.device(self.device):
-            self._wts = wts
-            try:
-                self._load(ds)
-            finally:
-                self._wts = None
-            st = stream_handle(self.device)
-            wd = w.detach().to(self.device, torch.float32).reshape(-1).contiguous()
-            g = torch.empty(s.P, dtype=torch.float32, device=self.device)
-            loss = self._native.loss_grad(wd.data_ptr(), g.data_ptr(), st)
-            return float(loss), g, float(self._native.holdout_loss(st))
-
-    def loss_grad(self, ds, w: torch.Tensor, weights: FitWeights | None = None):
-        """As :meth:`_FitterBase.loss_grad`; with ``weights`` the weighted mean loss of the
-        training rows and its gradient."""
-        if weights is None:
-            if self._native is not None and self._native.weighted:  # the resident rows keep their statistics pass
-                with torch.cuda.device(self.device):
-                    self._native.set_weights(stream=stream_handle(self.device))
-                if self._data is not None:
-                    self._data.applied = None
-            return super().loss_grad(ds, w)
-        return self._eval_weighted(ds, w, self._weighted(ds, weights, 1))[:2]
-
-    def holdout_loss(self, ds, w: torch.Tensor, weights: FitWeights) -> float:
-        """The held-out fold's weighted mean loss at ``w``: one raw evaluation."""
-        wts = self._weighted(ds, weights, 1)
-        if wts.holdout < 0:
-            raise ValueError("holdout_loss needs FitWeights.holdout")
-        return self._eval_weighted(ds, w, wts)[2]
-
-    def fit(self, train, w0: torch.Tensor | None = None, valid=None, valid_every: int = 1,
-            patience: int | None = None, weights: FitWeights | None = None) -> FitResult:
-        """As :meth:`_FitterBase.fit`; with ``weights`` the weighted objective, and
-        ``holdout_log_loss`` from one raw evaluation at the returned weights."""
-        if weights is None:
-            return super().fit(train, w0, valid, valid_every, patience)
-        wts = self._weighted(train, weights, 2)
-        self._wts = wts
-        try:
-            res = super().fit(train, w0, valid, valid_every, patience)
-        finally:
-            self._wts = None
-        if wts.holdout >= 0:
-            res.holdout_log_loss = self._eval_weighted(train, res.w, wts)[2]
-        return res
+        X, y = self._rows64(ds)
+        wc = w.detach().double().cpu()
+        loss, gc, gb = weighted_loss_grad(X, y, s.coef(wc), s.intercept(wc), wts.u)
+        ho = weighted_loss_grad(X, y, s.coef(wc), s.intercept(wc), wts.h)[0]
+        return float(loss), s.pack(gc, gb, device=self.device), float(ho)
 
     def _result_vector(self, w0):
         return torch.empty(self.spec.P, dtype=torch.float32, device=self.device)  # finalize writes all of it
@@ -537,11 +539,14 @@ class CVResult:
     seconds: float
 
 
-def cross_validate(spec: ModelSpec, ds: Dataset, reg_params, folds: int = 5, seed: int = 0, device="cpu",
-                   opts: FitOptions | None = None, sample_weight=None, class_weight=None) -> CVResult:
+def cross_validate(spec, ds, reg_params, folds: int = 5, seed: int = 0, device="cpu",
+                   opts: FitOptions | None = None, sample_weight=None, class_weight=None,
+                   col_chunk: int | None = None) -> CVResult:
     """K-fold choice of ``reg_param``: fold ids are drawn once, the rows are made resident
     once, and the ``folds * len(reg_params)`` fits differ only in the held-out fold (one
-    statistics pass, no copy) and the penalty.  The best penalty has the lowest mean
+    statistics pass, no copy) and the penalty.  A ``WideSpec`` with a ``SparseDataset``
+    runs the wide fitter (``col_chunk`` as :class:`psx.ops.wide_fit.WideFitter`): its
+    touched features, inverted index and work items are built once for all the fits.  The best penalty has the lowest mean
     held-out loss (the first of equals).  ``ds`` and ``sample_weight`` must not change
     while it runs: every fit reuses the first one's resident copies (see :class:`FitWeights`)."""
     regs = [float(r) for r in reg_params]
@@ -553,7 +558,12 @@ def cross_validate(spec: ModelSpec, ds: Dataset, reg_params, folds: int = 5, see
     o = opts or FitOptions()
     if is_gpu(torch.device(device)):
         ds = ds.to(device)
-    f = BatchFitter(spec, device, o)
+    if isinstance(spec, WideSpec):
+        from .wide_fit import WideFitter
+
+        f = WideFitter(spec, device, o, col_chunk=col_chunk)
+    else:
+        f = BatchFitter(spec, device, o)
     losses = []
     for r in regs:
         f.opts = FitOptions(**{**asdict(o), "reg_param": r})

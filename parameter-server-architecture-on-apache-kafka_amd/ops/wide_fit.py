@@ -16,6 +16,16 @@ one-time structures (sorted feature ids, compact columns, inverted index, work i
 are built with torch on the device.  Columns longer than ``col_chunk`` entries are cut
 into chunks of that size, one work item each, summed in chunk order.
 
+Row weights and a held-out fold (:class:`psx.ops.fit.FitWeights`, ``weights=`` of
+:meth:`WideFitter.fit` / :meth:`WideFitter.loss_grad`, the objective of
+:mod:`psx.ops.fit`): ``csrc/kernels/wide_fit_weighted.hip``.  The touched features, the
+inverted index and the work items stay those of the whole dataset; a weighted call on
+the same dataset object reuses them, and another held-out fold costs one pass over the
+rows' weights and one statistics pass -- :func:`psx.ops.fit.cross_validate` chooses
+``reg_param`` that way.  sigma is the weighted sample std over the training rows; a
+feature that takes one value on the rows of positive training weight (absent = 0), one
+only held-out or zero-weight rows touch included, is excluded like a constant one.
+
 CPU: :func:`psx.models.reference.fit_reference` on float64 sparse closures (the CSR
 matrix over the touched columns and its transpose); no ``N x F`` matrix is built.
 """
@@ -77,7 +87,9 @@ class _Index:
 
     def __init__(self, spec: WideSpec, ds: SparseDataset, device):
         self.src = ds
-        self.N = ds.rows
+        self.N = self.Npad = ds.rows  # (the weight streams are [N]: no padding rows)
+        self.wcache = {}  # device copies of a weighted call's sample weights / fold ids
+        self.applied = None  # the checked weights the native fitter holds for these rows
         self.indptr = ds.indptr.to(device, torch.int64).contiguous()
         self.val = ds.val.to(device, torch.bfloat16).contiguous()
         self.y = ds.y.to(device, torch.int32).contiguous()
@@ -120,9 +132,14 @@ class _Resident(_Index):
         self.long_items = torch.nonzero(~short).view(-1).to(torch.int32)
 
 
-def _closures(ix: _Index, K: int):
-    """float64 ``loss_grad(coef_eff [K, U], b [K])`` and sigma [U] of the rows behind ``ix`` (CPU)."""
+def _closures(ix: _Index, K: int, u=None):
+    """float64 ``loss_grad(coef_eff [K, U], b [K])`` and sigma [U] of the rows behind ``ix``
+    (CPU); with row weights ``u`` [N] the weighted mean loss ``(1/W) sum u loss``, its
+    gradient and the weighted sigma (``W = sum u``; all zeros when W is 0)."""
     N, U = ix.N, ix.U
+    if u is not None:
+        u = u.double()
+        W = u.sum()
     val = ix.val.double()
     with warnings.catch_warnings():  # "sparse CSR support is in beta"
         warnings.simplefilter("ignore", UserWarning)
@@ -135,13 +152,18 @@ def _closures(ix: _Index, K: int):
         if K == 1:
             zz = z[:, 0]
             yy = (y > 0).to(z.dtype)
-            loss = (torch.nn.functional.softplus(zz) - yy * zz).mean()
+            nll = torch.nn.functional.softplus(zz) - yy * zz
             r = (torch.sigmoid(zz) - yy).view(-1, 1)
         else:
-            loss = (torch.logsumexp(z, dim=1) - z.gather(1, y.view(-1, 1)).squeeze(1)).mean()
+            nll = torch.logsumexp(z, dim=1) - z.gather(1, y.view(-1, 1)).squeeze(1)
             r = torch.softmax(z, dim=1)
             r[torch.arange(N), y] -= 1.0
-        return loss, (At @ r).t() / N, r.sum(0) / N
+        if u is None:
+            return nll.mean(), (At @ r).t() / N, r.sum(0) / N
+        if float(W) == 0.0:
+            return torch.zeros((), dtype=z.dtype), torch.zeros_like(ce), torch.zeros_like(b)
+        r = r * u.view(-1, 1)
+        return (u * nll).sum() / W, (At @ r).t() / W, r.sum(0) / W
 
     # cells: entries of one column with the same row are adjacent in the inverted index and are summed first
     col_of = torch.repeat_interleave(torch.arange(U), ix.ccount)
@@ -151,12 +173,35 @@ def _closures(ix: _Index, K: int):
     cell = torch.cumsum(head, 0) - 1
     x = torch.zeros(int(head.sum()), dtype=torch.float64).index_add_(0, cell, ix.cval.double())
     ccol = col_of[head]
+    if u is not None:
+        return loss_grad, _weighted_sigma(U, ccol, x, u[ix.crow[head].long()], W, int((u > 0).sum()))
     present = torch.bincount(ccol, minlength=U).double()
     mean = torch.zeros(U, dtype=torch.float64).index_add_(0, ccol, x) / N
     sq = torch.zeros(U, dtype=torch.float64).index_add_(0, ccol, (x - mean[ccol]) ** 2)
     if N < 2:
         return loss_grad, torch.zeros(U, dtype=torch.float64)
     return loss_grad, ((sq + (N - present) * mean * mean) / (N - 1)).clamp_min(0).sqrt()
+
+
+def _weighted_sigma(U, ccol, x, uc, W, live_rows):
+    """Weighted sample std [U] from the cells (column ``ccol``, value ``x``, training
+    weight ``uc``), absent rows counting as zeros: two-pass, float64.  A feature with
+    one value on the ``live_rows`` rows of positive weight has sigma 0 exactly -- decided
+    on the live cells' count and their min / max, not on the rounded sums."""
+    zero = torch.zeros(U, dtype=torch.float64)
+    if not float(W) > 1.0:
+        return zero
+    mean = zero.clone().index_add_(0, ccol, uc * x) / W
+    wp = zero.clone().index_add_(0, ccol, uc)
+    sq = zero.clone().index_add_(0, ccol, uc * (x - mean[ccol]) ** 2)
+    sd = ((sq + (W - wp) * mean * mean) / (W - 1.0)).clamp_min(0).sqrt()
+    lv = uc > 0
+    cnt = torch.bincount(ccol[lv], minlength=U)
+    mn = torch.full((U,), float("inf"), dtype=torch.float64).scatter_reduce_(0, ccol[lv], x[lv], "amin")
+    mx = torch.full((U,), float("-inf"), dtype=torch.float64).scatter_reduce_(0, ccol[lv], x[lv], "amax")
+    part = cnt < live_rows  # a live row without a cell holds 0
+    mn, mx = torch.where(part, mn.clamp_max(0), mn), torch.where(part, mx.clamp_min(0), mx)
+    return torch.where((cnt > 0) & (mx > mn), sd, zero)
 
 
 class WideFitter(_FitterBase):
@@ -182,6 +227,16 @@ class WideFitter(_FitterBase):
         return hip.WideBatchFitter(self.spec.K, self.spec.KP, self.opts.hist, self.opts.max_wg or 0)
 
     def _load(self, ds: SparseDataset):
+        wts = self._wts
+        if wts is not None and self._data is not None and self._data.src is ds:
+            d = self._data  # weighted calls on one dataset object share its index (cross_validate)
+        else:
+            d = self._index(ds)
+        if wts is not None and self._native is not None and d.applied is not wts:
+            self._apply_weights(d, wts)  # the weights kernel and one statistics pass
+        return d
+
+    def _index(self, ds: SparseDataset):
         if self._native is None:
             self._data = _Index(self.spec, ds, self.device)
             return self._data
@@ -218,8 +273,12 @@ class WideFitter(_FitterBase):
     def _loss_grad_cpu(self, ds, w, resident):
         s = self.spec
         d = self._data if resident else self._load(ds)
+        return self._eval_cpu(d, w, None)
+
+    def _eval_cpu(self, d, w, u):
+        s = self.spec
         wc = w.detach().double().cpu().reshape(-1)
-        fg, _ = _closures(d, s.K)
+        fg, _ = _closures(d, s.K, u)
         rows = d.uniq.long()
         ce = wc[: s.F * s.KP].view(s.F, s.KP)[rows][:, : s.K].t()
         loss, gc, gb = fg(ce, s.intercept(wc))
@@ -228,10 +287,15 @@ class WideFitter(_FitterBase):
         g[s.F * s.KP: s.F * s.KP + s.K] = gb.float()
         return float(loss), g
 
+    def _eval_weighted_cpu(self, ds, w, wts):
+        d = self._load(ds)
+        loss, g = self._eval_cpu(d, w, wts.u)
+        return loss, g, self._eval_cpu(d, w, wts.h)[0]
+
     def _fit_cpu(self, train, w0, valid, valid_every, patience) -> FitResult:
         s, o = self.spec, self.opts
         d = self._load(train)
-        fg, sd = _closures(d, s.K)
+        fg, sd = _closures(d, s.K, self._wts.u if self._wts is not None else None)
         rows = d.uniq.long()
         c0, b0 = torch.zeros(s.K, d.U, dtype=torch.float64), None
         if w0 is not None:

@@ -12,8 +12,13 @@
   setup    seconds and device memory of loading the dataset (sorts, inverted index, items,
            statistics, workspace).
   fit      a full fit of the same rows: iterations, evaluations, seconds.
+  --weights  (instead of --what) one evaluation with row weights, class weights and a
+           held-out fold against the plain one by stage, the two alternating inside every
+           repeat; the fold switch (the weights kernel plus the weighted statistics, device
+           events around set_weights); and, with --cv FOLDS, the wall time of a
+           FOLDS x 3-penalty cross_validate of 10 iterations a fit.
 
-Usage: python tools/bench_wide_fit.py [--what eval,chunk,setup,fit] [--rows N] [--out FILE.json]
+Usage: python tools/bench_wide_fit.py [--what eval,chunk,setup,fit | --weights [--cv 5]] [--rows N] [--out FILE.json]
 """
 from __future__ import annotations
 
@@ -31,7 +36,7 @@ if ROOT not in sys.path:
 
 from psx import _native  # noqa: E402
 from psx.models.wide import WideSpec  # noqa: E402
-from psx.ops.fit import FitOptions  # noqa: E402
+from psx.ops.fit import FitOptions, FitWeights, _Weights, cross_validate  # noqa: E402
 from psx.ops.lr import stream_handle  # noqa: E402
 from psx.ops.wide_fit import DEFAULT_COL_CHUNK, WideFitter  # noqa: E402
 from psx.utils.data import synth_sparse  # noqa: E402
@@ -176,12 +181,44 @@ def bench_fit(dev, rows, K):
     return out
 
 
+def bench_weights(dev, rows, K, repeats, cv_folds):
+    spec = WideSpec(F, K)
+    ds = _data(dev, rows, K)
+    w = spec.init("random", seed=1, scale=0.05).to(dev)
+    g = torch.Generator().manual_seed(0)
+    wts = FitWeights(torch.rand(rows, generator=g) * 2, 0.5 + torch.rand(max(K, 2), generator=g),
+                     torch.randint(0, 5, (rows,), generator=g).to(torch.uint8), 0)
+    fitter = WideFitter(spec, dev)
+    st = stream_handle(dev)
+    fitter.loss_grad(ds, w, weights=wts)  # loads the dataset, copies the weight streams, warms up
+    data, nat = fitter._data, fitter._native
+    checked = [_Weights(spec, ds, FitWeights(wts.sample_weight, wts.class_weight, wts.fold, k)) for k in (0, 1)]
+    plain, weighted, switch = [], [], []
+    for i in range(repeats):
+        nat.set_weights(stream=st)
+        plain.append(nat.stage_ms(False, st))
+        switch.append(_event_ms(lambda: fitter._apply_weights(data, checked[i % 2])))
+        weighted.append(nat.stage_ms(False, st))
+    med = lambda runs: [_med([r[i] for r in runs]) for i in range(3)]  # noqa: E731
+    tot = sorted(sum(r) for r in plain)
+    out = {"rows": rows, "K": K, "plain_ms": med(plain), "weighted_ms": med(weighted),
+           "plain_eval_ms": _med(tot), "plain_eval_spread_ms": tot[-1] - tot[0],
+           "weighted_eval_ms": _med([sum(r) for r in weighted]), "fold_switch_ms": _med(switch)}
+    if cv_folds:
+        cv = cross_validate(spec, ds, [1e-4, 1e-3, 1e-2], folds=cv_folds, device=dev, opts=FitOptions(max_iter=10))
+        out.update(cv_folds=cv_folds, cv_seconds=cv.seconds, cv_means=cv.means)
+    print(json.dumps(out))
+    return out
+
+
 def main(argv=None) -> int:
     ap = argparse.ArgumentParser()
     ap.add_argument("--what", default="eval,chunk,setup,fit")
     ap.add_argument("--rows", type=int, default=1 << 20)
     ap.add_argument("--repeats", type=int, default=5)
     ap.add_argument("--out", default=None, help="also write the results as JSON")
+    ap.add_argument("--weights", action="store_true", help="the weighted evaluation against the plain one")
+    ap.add_argument("--cv", type=int, default=0, help="with --weights: folds of a timed cross_validate")
     a = ap.parse_args(argv)
     if not torch.cuda.is_available():
         print("bench_wide_fit: no GPU -- not measured", file=sys.stderr)
@@ -189,6 +226,12 @@ def main(argv=None) -> int:
     dev = torch.device("cuda:0")
     print(f"default col_chunk {DEFAULT_COL_CHUNK}")
     res = {}
+    if a.weights:
+        res["weights"] = [bench_weights(dev, a.rows, K, a.repeats, a.cv) for K in (6, 1)]
+        if a.out:
+            with open(a.out, "w") as f:
+                json.dump(res, f, indent=1)
+        return 0
     for what in a.what.split(","):
         if what == "eval":
             res[what] = [bench_eval(dev, a.rows, K, a.repeats) for K in (6, 1)]
