@@ -21,6 +21,7 @@
 #include "../kernels/lr_kernels.h"
 #include "../kernels/score_kernels.h"
 #include "../solver/fit.h"
+#include "../solver/fit_many.h"
 #include "../solver/solver.h"
 #include "../solver/wide_fit.h"
 #include "../solver/wide_solver.h"
@@ -408,7 +409,59 @@ PYBIND11_MODULE(_psx_hip, m) {
       .def_property_readonly("weighted", &BatchFitter::weighted)
       .def(
           "holdout_loss", [](BatchFitter& f, uintptr_t stream) { return f.holdout_loss(S(stream)); },
-          py::arg("stream") = 0);
+          py::arg("stream") = 0)
+      // Many fits per read of the rows (csrc/solver/fit_many.h).  Job m: penalty regs[m], held-out fold
+      // holdouts[m] (< 0: none), start w0s[m] (0: zeros); its weights -> w_out + m * n, its sigma -> std_out + m * FP.
+      .def_property_readonly("many_capacity", [](BatchFitter& f) { return many_capacity(f.width(), f.classes()); })
+      .def_property_readonly("many_round_seconds", [](BatchFitter& f) { return f.many().round_seconds(); })
+      .def(
+          "fit_many",
+          [](BatchFitter& f, uintptr_t sample_weight, const std::vector<float>& class_weight, uintptr_t fold,
+             const std::vector<double>& regs, const std::vector<int>& holdouts, const std::vector<uintptr_t>& w0s,
+             int max_iter, double tol, int ls_max, bool zero_const, uintptr_t w_out, uintptr_t std_out,
+             uintptr_t stream) {
+            if (!class_weight.empty() && (int)class_weight.size() != f.classes())
+              throw std::invalid_argument("fit_many: one class weight per class");
+            if (regs.size() != holdouts.size() || regs.size() != w0s.size())
+              throw std::invalid_argument("fit_many: one penalty, held-out fold and start per job");
+            std::vector<FitManyJob> jobs(regs.size());
+            for (size_t m = 0; m < jobs.size(); ++m) jobs[m] = {regs[m], holdouts[m], P<const float>(w0s[m])};
+            FitOpts o;
+            o.max_iter = max_iter;
+            o.tol = tol;
+            o.ls_max = ls_max;
+            o.zero_const = zero_const ? 1 : 0;
+            std::vector<FitManyResult> res;
+            {
+              py::gil_scoped_release nogil;
+              res = f.many().fit(P<const float>(sample_weight), class_weight.empty() ? nullptr : class_weight.data(),
+                                 P<const uint8_t>(fold), jobs, o, P<float>(w_out), P<float>(std_out), S(stream));
+            }
+            py::list out;
+            for (const auto& r : res)
+              out.append(py::make_tuple(r.objective, r.log_loss, r.history, r.accepted, r.evals, r.reason, r.ls_fail));
+            return out;
+          },
+          py::arg("sample_weight"), py::arg("class_weight"), py::arg("fold"), py::arg("regs"), py::arg("holdouts"),
+          py::arg("w0s"), py::arg("max_iter"), py::arg("tol"), py::arg("ls_max"), py::arg("zero_const"),
+          py::arg("w_out"), py::arg("std_out"), py::arg("stream") = 0)
+      // One raw evaluation of M weight vectors ws [M][n] -> (losses, held-out losses), gradients -> grads [M][n].
+      .def(
+          "loss_grad_many",
+          [](BatchFitter& f, uintptr_t sample_weight, const std::vector<float>& class_weight, uintptr_t fold,
+             uintptr_t ws, const std::vector<int>& holdouts, uintptr_t grads, uintptr_t stream) {
+            if (!class_weight.empty() && (int)class_weight.size() != f.classes())
+              throw std::invalid_argument("loss_grad_many: one class weight per class");
+            std::vector<FitManyJob> jobs(holdouts.size());
+            for (size_t m = 0; m < jobs.size(); ++m)
+              jobs[m] = {0.0, holdouts[m], ws ? P<const float>(ws) + m * (size_t)f.n() : nullptr};
+            std::vector<double> losses, ho;
+            f.many().loss_grad(P<const float>(sample_weight), class_weight.empty() ? nullptr : class_weight.data(),
+                               P<const uint8_t>(fold), jobs, P<float>(grads), losses, ho, S(stream));
+            return py::make_tuple(losses, ho);
+          },
+          py::arg("sample_weight"), py::arg("class_weight"), py::arg("fold"), py::arg("ws"), py::arg("holdouts"),
+          py::arg("grads"), py::arg("stream") = 0);
   py::class_<WideBatchFitter, FitDriver>(m, "WideBatchFitter")
       .def(py::init<int, int, int, int>(), py::arg("K"), py::arg("KP"), py::arg("hist") = 10, py::arg("max_wg") = 0)
       .def(

@@ -85,7 +85,8 @@ def _local_includes(src):
 # verified with.  The arithmetic is the same IEEE fp32 either way; only the compiler's
 # choice between fused and unfused forms can differ (see fit_reduce_w_kernel).
 NO_PACKED_FP32 = ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"]
-EXTRA_CFLAGS = {"fit_weighted.hip": NO_PACKED_FP32, "wide_fit_weighted.hip": NO_PACKED_FP32}
+EXTRA_CFLAGS = {"fit_weighted.hip": NO_PACKED_FP32, "wide_fit_weighted.hip": NO_PACKED_FP32,
+                "fit_many.hip": NO_PACKED_FP32}  # (both files of that name: kernels/ and solver/)
 
 
 def _compile_link(compiler, sources, out, cflags, ldflags, jobs, objdir, headers=()):
@@ -95,7 +96,8 @@ def _compile_link(compiler, sources, out, cflags, ldflags, jobs, objdir, headers
     objs = []
     cmds = []
     for s in sources:
-        o = os.path.join(objdir, os.path.basename(s) + ".o")
+        # (kernels/fit_many.hip and solver/fit_many.hip: the directory is part of the object's name)
+        o = os.path.join(objdir, os.path.basename(os.path.dirname(s)) + "_" + os.path.basename(s) + ".o")
         objs.append(o)
         flags = cflags + EXTRA_CFLAGS.get(os.path.basename(s), [])
         dig = _hash(_local_includes(s), flags)

@@ -13,11 +13,15 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include <memory>
+
 #include "../kernels/fit_kernels.h"
 #include "../kernels/fit_weighted.h"
 #include "fit_driver.h"
 
 namespace psx {
+
+class FitMany;
 
 class BatchFitter : public FitDriver {
  public:
@@ -40,8 +44,13 @@ class BatchFitter : public FitDriver {
                    hipStream_t s);
   bool weighted() const { return weighted_; }
   int classes() const { return dv_.K; }
+  int width() const { return dv_.FP; }
   // The held-out rows' weighted mean loss at the last evaluation (0 without held-out weight).
   double holdout_loss(hipStream_t s);
+  // Many fits per read of the rows (fit_many.h) on the resident rows; its workspace is
+  // built on first use and dropped by set_data.  It keeps vectors of its own: a fit in
+  // progress and the weights set here are left as they are.
+  FitMany& many();
 
  protected:
   // the weights are [K*FP + K]; the vectors exist from construction
@@ -59,6 +68,7 @@ class BatchFitter : public FitDriver {
   bool weighted_ = false;
   void* ws_ = nullptr;
   void* data_ws_ = nullptr;  // per-dataset partials (sized by the grid)
+  std::unique_ptr<FitMany> many_;
 };
 
 }  // namespace psx

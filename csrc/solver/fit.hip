@@ -3,6 +3,7 @@
 #include <climits>
 #include <stdexcept>
 
+#include "fit_many.h"
 #include "solver.h"
 
 namespace psx {
@@ -45,6 +46,7 @@ void BatchFitter::set_data(const uint16_t* X, const int32_t* y, int64_t N, int64
   if (Npad != (N + 31) / 32 * 32) throw std::invalid_argument("the rows must be padded to a multiple of 32");
   if (!X || !y) throw std::invalid_argument("null rows or labels");
   end_fit();
+  many_.reset();
   weighted_ = false;
   wd_.sw = nullptr;
   wd_.fold = nullptr;
@@ -95,6 +97,12 @@ void BatchFitter::set_weights(const float* sample_weight, const float* class_wei
   weighted_ = true;
   launch_fit_stats_w(dv_, wd_, G_, s);
   hip_check(hipGetLastError(), "fit_stats_w launch");
+}
+
+FitMany& BatchFitter::many() {
+  if (!dv_.X) throw std::runtime_error("fit_many: no dataset (set_data first)");
+  if (!many_) many_ = std::make_unique<FitMany>(dv_, wd_, G_);
+  return *many_;
 }
 
 double BatchFitter::holdout_loss(hipStream_t s) {

@@ -55,54 +55,70 @@ class FitLoop {
     done_ = true;
   }
 
+  // Whether another evaluation is due; ends the fit once the evaluation budget is spent
+  // (never expected: every line search ends within ls_max evaluations).
+  bool wants_eval() {
+    if (!begun_) throw std::runtime_error("fit: begin() first");
+    if (done_) return false;
+    if (ctrl_.evals >= max_evals_) {
+      reason_ = "max_iter";
+      done_ = true;
+      return false;
+    }
+    return true;
+  }
+
+  // Consume one evaluation already made at the trial point (its result block in `pin`):
+  // the controller step, the history and, through apply(step), the action; true: ended.
+  // Several fits advanced in lockstep (fit_many.hip) call this once per fit and round.
+  template <class Apply>
+  bool step(const double* pin, Apply&& apply) {
+    const double f_t = pin[kFitOutF];
+    const int phase0 = ctrl_.phase, nacc_prev = ctrl_.nacc;
+    ctrl_step(ctrl_, cfg_, f_t, pin + kFitOutDots, slot_, scratch_);
+    if (slot_ < INT_MAX - 2) ++slot_;
+    if (phase0 == kPhInit) {
+      history_.push_back(f_t);
+      log_loss_ = pin[kFitOutLoss];
+    } else if (ctrl_.nacc > nacc_prev) {
+      history_.push_back(ctrl_.f_c);
+      log_loss_ = pin[kFitOutLoss];
+    }
+    if (ctrl_.action != kActDone && ctrl_.action != kActNone) {
+      FitStep st{};
+      st.action = ctrl_.action;
+      st.push_slot = ctrl_.push_slot;
+      st.t = ctrl_.t;
+      st.t_acc = ctrl_.t_acc;
+      st.cg = ctrl_.cg;
+      for (int i = 0; i < kMaxHist; ++i) {
+        st.cs[i] = ctrl_.cs[i];
+        st.cy[i] = ctrl_.cy[i];
+      }
+      apply(st);
+    }
+    if (ctrl_.phase == kPhDone) {
+      done_ = true;
+      const bool finite = std::isfinite(f_t);
+      if (ctrl_.action == kActAcceptDone)
+        reason_ = ctrl_.iter >= cfg_.iters ? "max_iter" : "tol";
+      else if (phase0 == kPhInit)  // ended at the starting point
+        reason_ = !finite ? "no_descent" : (cfg_.iters <= 0 ? "max_iter" : "tol");
+      else  // a line search spent its budget without sufficient decrease (or met a non-finite objective)
+        reason_ = finite ? "line_search" : "no_descent";
+    }
+    return done_;
+  }
+
   // Evaluate until the fit ends or `max_accept` more steps were accepted; true: ended.
   // evaluate(reg_param) leaves the result block in `pin`; apply(step) applies one action.
   template <class Eval, class Apply>
   bool run(int max_accept, const double* pin, Eval&& evaluate, Apply&& apply) {
     if (!begun_) throw std::runtime_error("fit: begin() first");
     const int nacc0 = ctrl_.nacc;
-    while (!done_) {
-      if (ctrl_.evals >= max_evals_) {  // never expected: every line search ends within ls_max evaluations
-        reason_ = "max_iter";
-        done_ = true;
-        break;
-      }
+    while (wants_eval()) {
       evaluate(opts_.reg_param);
-      const double f_t = pin[kFitOutF];
-      const int phase0 = ctrl_.phase, nacc_prev = ctrl_.nacc;
-      ctrl_step(ctrl_, cfg_, f_t, pin + kFitOutDots, slot_, scratch_);
-      if (slot_ < INT_MAX - 2) ++slot_;
-      if (phase0 == kPhInit) {
-        history_.push_back(f_t);
-        log_loss_ = pin[kFitOutLoss];
-      } else if (ctrl_.nacc > nacc_prev) {
-        history_.push_back(ctrl_.f_c);
-        log_loss_ = pin[kFitOutLoss];
-      }
-      if (ctrl_.action != kActDone && ctrl_.action != kActNone) {
-        FitStep st{};
-        st.action = ctrl_.action;
-        st.push_slot = ctrl_.push_slot;
-        st.t = ctrl_.t;
-        st.t_acc = ctrl_.t_acc;
-        st.cg = ctrl_.cg;
-        for (int i = 0; i < kMaxHist; ++i) {
-          st.cs[i] = ctrl_.cs[i];
-          st.cy[i] = ctrl_.cy[i];
-        }
-        apply(st);
-      }
-      if (ctrl_.phase == kPhDone) {
-        done_ = true;
-        const bool finite = std::isfinite(f_t);
-        if (ctrl_.action == kActAcceptDone)
-          reason_ = ctrl_.iter >= cfg_.iters ? "max_iter" : "tol";
-        else if (phase0 == kPhInit)  // ended at the starting point
-          reason_ = !finite ? "no_descent" : (cfg_.iters <= 0 ? "max_iter" : "tol");
-        else  // a line search spent its budget without sufficient decrease (or met a non-finite objective)
-          reason_ = finite ? "line_search" : "no_descent";
-        break;
-      }
+      if (step(pin, apply)) break;
       if (ctrl_.nacc - nacc0 >= max_accept) break;
     }
     return done_;

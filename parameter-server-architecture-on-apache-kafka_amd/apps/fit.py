@@ -3,7 +3,7 @@
 Usage: python -m psx.apps.fit --train train.csv [--test test.csv] [--valid valid.csv | --valid_frac 0.1 --seed 0]
            [--reg_param 0] [--max_iter 100] [--tol 1e-6] [--init_checkpoint DIR] [--checkpoint_dir OUT]
            [--device ...] [--header auto|yes|no] [--label_col -1] [--num_classes K]
-           [--class_weight balanced|w0,w1,...] [--cv K --reg_params a,b,c]
+           [--class_weight balanced|w0,w1,...] [--cv K --reg_params a,b,c [--cv_batch auto|N]]
        python -m psx.apps.fit --train train.svm [--num_features F] [--sigmoid] [--zero_based] [...]
 
 CSVs and binary row caches fit the dense model.  A LIBSVM file (``.svm``, ``.libsvm``,
@@ -14,7 +14,8 @@ the iterates on held-out rows and keep the best one (``--patience N`` stops afte
 without improvement).  ``--class_weight`` weighs the rows by their class (``balanced``:
 N / (classes present * class count); with ``--sigmoid`` two weights, ``w0,w1``); ``--cv K --reg_params a,b,c`` runs a
 K-fold cross-validation of the penalties on the resident rows, prints its table to stderr
-and fits the whole set at the best one (it excludes ``--valid`` / ``--valid_frac``).
+and fits the whole set at the best one (it excludes ``--valid`` / ``--valid_frac``); ``--cv_batch auto|N``
+runs its fits N at a time on one read of the rows per evaluation (dense model, a class-weight table).
 ``--checkpoint_dir`` gets a ``server.ckpt`` that
 ``python -m psx.apps.predict`` reads.  stdout gets one JSON line: rows, features,
 classes, iterations, evaluations, reason, objective, train log-loss, the test metrics
@@ -56,6 +57,7 @@ def fit_parser():
     ap.add_argument("--class_weight", default=None, help="'balanced' or one weight per class, w0,w1,... (--sigmoid: w0,w1)")
     ap.add_argument("--cv", type=int, default=0, help="folds of a cross-validation over --reg_params")
     ap.add_argument("--reg_params", default=None, help="penalties --cv compares, a,b,c")
+    ap.add_argument("--cv_batch", default=None, help="'auto' or N: fits of --cv that share one read of the rows")
     return ap
 
 
@@ -83,6 +85,8 @@ def main(argv=None) -> int:
         ap.error("--cv excludes --valid and --valid_frac")
     if bool(a.cv) != bool(a.reg_params):
         ap.error("--cv and --reg_params go together")
+    if a.cv_batch is not None and (not a.cv or not (a.cv_batch == "auto" or (a.cv_batch.isdigit() and int(a.cv_batch)))):
+        ap.error("--cv_batch is 'auto' or a positive number and goes with --cv")
     from ..models.logreg import ModelSpec
     from ..models.wide import WideSpec
     from ..ops.fit import BatchFitter, FitOptions, FitWeights, cross_validate
@@ -138,7 +142,8 @@ def main(argv=None) -> int:
         if a.cv:
             regs = [float(v) for v in a.reg_params.split(",")]
             cv = cross_validate(spec, train, regs, folds=a.cv, seed=a.seed, device=device, class_weight=cw,
-                                opts=FitOptions(max_iter=a.max_iter, tol=a.tol))
+                                opts=FitOptions(max_iter=a.max_iter, tol=a.tol),
+                                batch=None if a.cv_batch is None else a.cv_batch if a.cv_batch == "auto" else int(a.cv_batch))
             for r, row, m in zip(cv.reg_params, cv.losses, cv.means):
                 print(f"reg_param {r:<10g} held-out loss " + " ".join(f"{v:.6f}" for v in row) + f"  mean {m:.6f}",
                       file=sys.stderr)

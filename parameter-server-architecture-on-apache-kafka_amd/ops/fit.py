@@ -26,6 +26,13 @@ weighted mean loss (``FitResult.holdout_log_loss``).  GPU:
 fold costs one statistics pass and no copy -- :func:`cross_validate` chooses
 ``reg_param`` that way.
 
+Many fits per read of the rows (:class:`FitJob`, :meth:`BatchFitter.fit_many`,
+``cross_validate(batch=...)``): the fits of a grid share the rows, the labels and the
+weight streams and differ in the held-out fold, the penalty and the iterate, so one
+staged tile serves several of them -- ``csrc/kernels/fit_many.hip`` packs the models into
+the MFMA columns a single ``K``-class model leaves empty and ``csrc/solver/fit_many.hip``
+advances all fits in lockstep, one evaluation round at a time.
+
 fp32 rows are converted to bf16, as :class:`psx.ops.score.Scorer` does: the fit sees
 the rounded features.
 
@@ -39,7 +46,7 @@ from __future__ import annotations
 import os
 import statistics
 import time
-from dataclasses import asdict, dataclass, field
+from dataclasses import asdict, dataclass, field, replace
 
 import torch
 
@@ -151,6 +158,15 @@ class FitWeights:
     class_weight: torch.Tensor | str | None = None  # [K], or "balanced": N_train / (K_present * count_c)
     fold: torch.Tensor | None = None  # [N] fold ids in 0..255
     holdout: int | None = None
+
+
+@dataclass
+class FitJob:
+    """One fit of :meth:`BatchFitter.fit_many`: its penalty, its held-out fold (a fold id of
+    the shared ``FitWeights.fold``) and its start (device layout ``[P]``; None: zeros)."""
+    reg_param: float
+    holdout: int | None = None
+    w0: torch.Tensor | None = None
 
 
 class _Weights:
@@ -295,9 +311,9 @@ class _FitterBase:
         self._check_data(self.spec, ds, min_rows)
         return _Weights(self.spec, ds, weights)
 
-    def _apply_weights(self, data, wts):
-        """Hand ``wts`` to the native fitter for the resident ``data`` (a statistics pass, no copy of the rows)."""
-        def padded(v, src, dtype):  # [Npad] on the device; one copy per source tensor
+    def _streams(self, data, wts):
+        """The padded device copies of ``wts``'s sample weights and fold ids (or None): one copy per source tensor."""
+        def padded(v, src, dtype):  # [Npad] on the device
             if v is None:
                 return None
             if data.wcache.get(dtype, (None, None))[0] is not src:
@@ -306,8 +322,11 @@ class _FitterBase:
                 data.wcache[dtype] = (src, t)
             return data.wcache[dtype][1]
 
-        sw = padded(wts.sw, wts.src.sample_weight, torch.float32)
-        fold = padded(wts.fold, wts.src.fold, torch.uint8)
+        return padded(wts.sw, wts.src.sample_weight, torch.float32), padded(wts.fold, wts.src.fold, torch.uint8)
+
+    def _apply_weights(self, data, wts):
+        """Hand ``wts`` to the native fitter for the resident ``data`` (a statistics pass, no copy of the rows)."""
+        sw, fold = self._streams(data, wts)
         self._native.set_weights(sw.data_ptr() if sw is not None else 0,
                                  wts.cw.tolist() if wts.cw is not None else [],
                                  fold.data_ptr() if fold is not None else 0, wts.holdout, stream_handle(self.device))
@@ -369,6 +388,104 @@ class _FitterBase:
             g = torch.empty(s.P, dtype=torch.float32, device=self.device)
             loss = self._native.loss_grad(wd.data_ptr(), g.data_ptr(), stream_handle(self.device))
         return float(loss), g
+
+    # ---- many fits per read of the rows ----------------------------------------------
+    def _many_setup(self, ds, weights, holdouts, min_rows):
+        """Checks of a batched call (ValueError before any launch) -> the checked weights of every distinct
+        held-out fold, in the jobs' order."""
+        if isinstance(self.spec, WideSpec):
+            raise ValueError("fit_many / loss_grad_many serve the dense model (ModelSpec), not the wide one")
+        weights = weights or FitWeights()
+        if weights.holdout is not None:
+            raise ValueError("the shared FitWeights of a batched call hold no fold out: every job names its own")
+        if not holdouts:
+            raise ValueError("a batched call needs at least one job")
+        if isinstance(weights.class_weight, str) and len(set(holdouts)) > 1:
+            raise ValueError("'balanced' class weights depend on the held-out fold; a batched call shares one table")
+        return [self._weighted(ds, replace(weights, holdout=h), min_rows) for h in dict.fromkeys(holdouts)]
+
+    def _many_resident(self, ds, wts):
+        """The resident rows of ``ds`` and the native arguments of the shared streams."""
+        if self._data is None or self._data.src is not ds:
+            self._load(ds)
+        data = self._data
+        sw, fold = self._streams(data, wts)
+        return data, (sw.data_ptr() if sw is not None else 0, wts.cw.tolist() if wts.cw is not None else [],
+                      fold.data_ptr() if fold is not None else 0)
+
+    def loss_grad_many(self, ds, ws, weights: FitWeights | None, holdouts):
+        """One raw evaluation of the M weight vectors ``ws`` (``[M, P]``, device layout; no standardisation,
+        no penalty), vector m with fold ``holdouts[m]`` (or None) held out, on ONE read of the rows per
+        ``many_capacity`` vectors -> ``(losses [M], grads [M, P], holdout_losses [M])``."""
+        holdouts = list(holdouts)
+        checked = self._many_setup(ds, weights, holdouts, 1)
+        ws = torch.stack(list(ws)) if not isinstance(ws, torch.Tensor) else ws
+        if ws.dim() != 2 or ws.shape != (len(holdouts), self.spec.P):
+            raise ValueError(f"{len(holdouts)} weight vectors of {self.spec.P} are needed, got {tuple(ws.shape)}")
+        if self._native is None:
+            by = dict(zip(dict.fromkeys(holdouts), checked))
+            rows = [self._eval_weighted(ds, w, by[h]) for w, h in zip(ws, holdouts)]
+            return (torch.tensor([r[0] for r in rows], dtype=torch.float64), torch.stack([r[1] for r in rows]),
+                    torch.tensor([r[2] for r in rows], dtype=torch.float64))
+        with torch.cuda.device(self.device):
+            _, streams = self._many_resident(ds, checked[0])
+            wd = ws.detach().to(self.device, torch.float32).contiguous()
+            g = torch.empty_like(wd)
+            loss, ho = self._native.loss_grad_many(*streams, wd.data_ptr(), [-1 if h is None else int(h) for h in holdouts],
+                                                   g.data_ptr(), stream_handle(self.device))
+        return torch.tensor(loss, dtype=torch.float64), g, torch.tensor(ho, dtype=torch.float64)
+
+    @property
+    def many_capacity(self) -> int:
+        """Models one read of the rows serves on the GPU: a function of the padded width and the class count."""
+        return int(self._native.many_capacity)
+
+    def fit_many(self, train, jobs, weights: FitWeights | None = None) -> list:
+        """Fit every :class:`FitJob` on ``train``: result i is what ``fit(train, w0=jobs[i].w0,
+        weights=FitWeights(..., holdout=jobs[i].holdout))`` returns under ``reg_param = jobs[i].reg_param``.
+        ``weights`` carries the shared ``sample_weight``, ``class_weight`` and ``fold`` (its own ``holdout``
+        stays None); the other options are the fitter's.  On the GPU all fits advance in lockstep, each
+        evaluation round reading the rows once per ``many_capacity`` unfinished jobs; a job's result does
+        not depend on the jobs beside it.  ``FitResult.seconds`` is the whole batch's."""
+        jobs = list(jobs)
+        checked = self._many_setup(train, weights, [j.holdout for j in jobs], 2)
+        s, o = self.spec, self.opts
+        for j in jobs:
+            _check_options(replace(o, reg_param=float(j.reg_param)))
+            if j.w0 is not None and j.w0.numel() != s.P:
+                raise ValueError(f"the model has {s.P} weights in device layout, got {j.w0.numel()}")
+        if self._native is None:
+            out = []
+            try:
+                for j in jobs:
+                    self.opts = replace(o, reg_param=float(j.reg_param))
+                    out.append(self.fit(train, w0=j.w0, weights=replace(weights or FitWeights(), holdout=j.holdout)))
+            finally:
+                self.opts = o
+            return out
+        t0 = time.perf_counter()
+        with torch.cuda.device(self.device):
+            st, nat, M = stream_handle(self.device), self._native, len(jobs)
+            _, streams = self._many_resident(train, checked[0])
+            w0s = [None if j.w0 is None else j.w0.detach().to(self.device, torch.float32).reshape(-1).contiguous()
+                   for j in jobs]
+            holds = [-1 if j.holdout is None else int(j.holdout) for j in jobs]
+            w = torch.empty(M, s.P, dtype=torch.float32, device=self.device)
+            std = torch.empty(M, s.Fp, dtype=torch.float32, device=self.device)
+            rows = nat.fit_many(*streams, [float(j.reg_param) for j in jobs], holds,
+                                [0 if t is None else t.data_ptr() for t in w0s], int(o.max_iter), float(o.tol),
+                                int(o.ls_max), bool(o.zero_const), w.data_ptr(), std.data_ptr(), st)
+            ev = list(nat.many_round_seconds)
+            ho = None
+            if any(h >= 0 for h in holds):  # one more round: every job's held-out loss at its returned weights
+                ho = nat.loss_grad_many(*streams, w.data_ptr(), holds, torch.empty_like(w).data_ptr(), st)[1]
+        dt = time.perf_counter() - t0
+        return [FitResult(spec=s, w=w[m].clone(), objective=float(r[0]), log_loss=float(r[1]), history=list(r[2]),
+                          iters=int(r[3]), evals=int(r[4]), reason=str(r[5]), std=std[m, : s.F].clone(), seconds=dt,
+                          pass_seconds=statistics.median(ev) if ev else 0.0,
+                          options=replace(o, reg_param=float(jobs[m].reg_param)), ls_fail=int(r[6]),
+                          holdout_log_loss=float(ho[m]) if holds[m] >= 0 else None)
+                for m, r in enumerate(rows)]
 
     # ---- the fit ---------------------------------------------------------------
     def fit(self, train, w0: torch.Tensor | None = None, valid=None, valid_every: int = 1,
@@ -541,14 +658,20 @@ class CVResult:
 
 def cross_validate(spec, ds, reg_params, folds: int = 5, seed: int = 0, device="cpu",
                    opts: FitOptions | None = None, sample_weight=None, class_weight=None,
-                   col_chunk: int | None = None) -> CVResult:
+                   col_chunk: int | None = None, batch: int | str | None = None) -> CVResult:
     """K-fold choice of ``reg_param``: fold ids are drawn once, the rows are made resident
     once, and the ``folds * len(reg_params)`` fits differ only in the held-out fold (one
     statistics pass, no copy) and the penalty.  A ``WideSpec`` with a ``SparseDataset``
     runs the wide fitter (``col_chunk`` as :class:`psx.ops.wide_fit.WideFitter`): its
     touched features, inverted index and work items are built once for all the fits.  The best penalty has the lowest mean
     held-out loss (the first of equals).  ``ds`` and ``sample_weight`` must not change
-    while it runs: every fit reuses the first one's resident copies (see :class:`FitWeights`)."""
+    while it runs: every fit reuses the first one's resident copies (see :class:`FitWeights`).
+
+    ``batch``: None runs the fits one after another.  A number runs them that many at a time through
+    :meth:`BatchFitter.fit_many` (one read of the rows per evaluation round and ``many_capacity`` jobs),
+    ``"auto"`` all of them at once -- or one after another where a read of the rows serves a single
+    model (``many_capacity`` 1).  Dense model, a class-weight table or none; the held-out losses agree with
+    the sequential path to the fits' accuracy, not bit for bit."""
     regs = [float(r) for r in reg_params]
     if not regs or not 2 <= folds <= 255 or folds > ds.rows:
         raise ValueError("cross_validate needs penalties and 2 <= folds <= min(255, rows)")
@@ -564,6 +687,23 @@ def cross_validate(spec, ds, reg_params, folds: int = 5, seed: int = 0, device="
         f = WideFitter(spec, device, o, col_chunk=col_chunk)
     else:
         f = BatchFitter(spec, device, o)
+    if batch is not None and (isinstance(spec, WideSpec) or not (batch == "auto" or (isinstance(batch, int) and batch >= 1))):
+        raise ValueError("cross_validate(batch=...) is 'auto' or a number >= 1 and serves the dense model")
+    # "auto": batched wherever one read of the rows serves at least two models.  Measured on 2^20 rows, 5 folds x
+    # 4 penalties (profiles/r20/README.md): batched / sequential 0.174 / 0.352 s at width 1,024 with 6 classes,
+    # 0.045 / 0.152 s with 2, and faster in every other measured cell (widths 128, 512, 2,048; 2 and 6 classes).
+    # With capacity 1 (width 2,048, more than 8 classes) there is nothing to share: the sequential path.
+    if batch == "auto" and f._native is not None and f.many_capacity < 2:
+        batch = None
+    if batch is not None:
+        jobs = [FitJob(r, k) for r in regs for k in range(folds)]
+        step = len(jobs) if batch == "auto" else batch
+        shared, res = FitWeights(sample_weight, class_weight, fold), []
+        for i in range(0, len(jobs), step):
+            res += f.fit_many(ds, jobs[i: i + step], shared)
+        losses = [[res[i * folds + k].holdout_log_loss for k in range(folds)] for i in range(len(regs))]
+        means = [sum(row) / folds for row in losses]
+        return CVResult(regs, losses, means, regs[means.index(min(means))], fold, time.perf_counter() - t0)
     losses = []
     for r in regs:
         f.opts = FitOptions(**{**asdict(o), "reg_param": r})
@@ -575,4 +715,4 @@ def cross_validate(spec, ds, reg_params, folds: int = 5, seed: int = 0, device="
     return CVResult(regs, losses, means, regs[means.index(min(means))], fold, time.perf_counter() - t0)
 
 
-__all__ = ["BatchFitter", "CVResult", "FitOptions", "FitResult", "FitWeights", "cross_validate", "loss_grad"]
+__all__ = ["BatchFitter", "CVResult", "FitJob", "FitOptions", "FitResult", "FitWeights", "cross_validate", "loss_grad"]

@@ -11,12 +11,17 @@
            the same rows, alternating, 9 repeats; then one ``cross_validate`` run of
            5 folds x 4 penalties on them and the time of one fold switch (the
            weighted statistics pass).
+  eval --many   one evaluation round of M models on one read of the rows per many_capacity
+           models (csrc/kernels/fit_many.hip) for M = 1, capacity, 2 x capacity against M
+           weighted single-model evaluations, alternating, K = 6 and K = 2; then a
+           5-fold x 4-penalty ``cross_validate`` with ``batch="auto"`` against
+           ``batch=None``, alternating, medians of three.
   truth    BASELINE.md's ground-truth row: fit the 90k-row synthetic fine-food set with
            default options, score the 4,877-row test set.
   ceiling  a fit of --ceiling_rows x 1,024 rows drawn on the device from a planted
            softmax model (a size whose float64 copy no host holds).
 
-Usage: python tools/bench_fit.py [--what eval,truth,ceiling] [--weighted] [--rows N] [--ceiling_rows N] [--out FILE.json]
+Usage: python tools/bench_fit.py [--what eval,truth,ceiling] [--weighted | --many] [--rows N] [--ceiling_rows N] [--out FILE.json]
 """
 from __future__ import annotations
 
@@ -148,6 +153,60 @@ def bench_weighted(dev, rows: int, F: int = 1024, K: int = 6) -> dict:
     return out
 
 
+def bench_many(dev, rows: int, F: int = 1024, classes=(6, 2), repeats: int = 5) -> dict:
+    out = {"rows": rows, "features": F}
+    st = torch.cuda.current_stream(dev).cuda_stream
+    for K in classes:
+        spec = ModelSpec(F, K)
+        ds, W = planted(dev, rows, spec.Fp, K, seed=0)
+        if K == 2:  # (planted leaves class 0 out: two classes need labels of their own)
+            g = torch.Generator(device=dev).manual_seed(1)
+            ds.y.copy_(torch.cat([(xb.float() @ W[1] + torch.randn(xb.shape[0], generator=g, device=dev) > 0)
+                                  for xb in ds.X.split(1 << 18)]).to(torch.int32))
+        g = torch.Generator().manual_seed(0)
+        folds = (torch.randperm(rows, generator=g) % 5).to(torch.uint8)
+        wts = FitWeights(torch.rand(rows, generator=g) * 2, 0.5 + torch.rand(K, generator=g), folds)
+        f = BatchFitter(spec, dev)
+        gbuf = torch.empty(spec.P, device=dev)
+        cap0 = None
+        series = {}
+        for mult in (0, 1, 2):
+            M = max(1, mult * (cap0 or 1))
+            ws = torch.stack([spec.init("random", seed=m, scale=0.05) for m in range(M)]).to(dev)
+            holds = [m % 5 for m in range(M)]
+            one = FitWeights(wts.sample_weight, wts.class_weight, wts.fold, 0)
+            f.loss_grad_many(ds, ws, wts, holds)  # warm-up; the rows are resident from here on
+            cap0 = f.many_capacity
+            many_ms, seq_ms = [], []
+            for _ in range(repeats):  # alternate
+                f.loss_grad_many(ds, ws, wts, holds)
+                many_ms.append(1e3 * f._native.many_round_seconds[0])
+                f.loss_grad(ds, ws[0], weights=one)  # fold 0 held out; its statistics pass and host checks not timed
+                torch.cuda.synchronize()
+                t0 = time.perf_counter()  # the native call alone: begin, evaluation, reduction, the wait
+                f._native.loss_grad(ws[0].data_ptr(), gbuf.data_ptr(), st)
+                seq_ms.append(1e3 * (time.perf_counter() - t0))
+            series[M] = {"many_ms": many_ms, "single_ms": seq_ms}
+            a, b = _mmm(many_ms)[1], _mmm(seq_ms)[1]
+            print(f"FP {spec.Fp} K {K} capacity {cap0} M {M:3d}: one batched round {a:8.3f} ms (median of {repeats}), one single-model "
+                  f"evaluation {b:8.3f} ms, M of them {M * b:8.3f} ms -> x{M * b / a:.2f}")
+        cv = {"auto": [], "none": []}
+        kw = dict(folds=5, device=dev, opts=FitOptions(max_iter=20), sample_weight=wts.sample_weight,
+                  class_weight=wts.class_weight)
+        for _ in range(3):
+            for name, batch in (("auto", "auto"), ("none", None)):
+                torch.cuda.synchronize()
+                t0 = time.perf_counter()
+                r = cross_validate(spec, ds, [1e-4, 1e-3, 1e-2, 1e-1], batch=batch, **kw)
+                torch.cuda.synchronize()
+                cv[name].append(time.perf_counter() - t0)
+                cv[name + "_best"] = r.best_reg_param
+        print(f"FP {spec.Fp} K {K} cross_validate 5 folds x 4 penalties (max_iter 20): batch='auto' {_mmm(cv['auto'])[1]:.3f} s, "
+              f"batch=None {_mmm(cv['none'])[1]:.3f} s (medians of 3), best {cv['auto_best']} / {cv['none_best']}")
+        out[f"K{K}"] = {"capacity": cap0, "rounds": series, "cv": cv}
+    return out
+
+
 def _fit_report(name, res, extra=None):
     ev = res.evals
     line = {"case": name, "seconds": res.seconds, "iters": res.iters, "evals": ev, "reason": res.reason,
@@ -194,6 +253,9 @@ def main(argv=None) -> int:
     ap = argparse.ArgumentParser()
     ap.add_argument("--what", default="eval,truth")
     ap.add_argument("--weighted", action="store_true", help="eval: the plain against the weighted evaluation, and CV")
+    ap.add_argument("--many", action="store_true", help="eval: batched evaluation rounds and batched CV against sequential")
+    ap.add_argument("--features", type=int, default=1024, help="--many: row width")
+    ap.add_argument("--classes", default="6,2", help="--many: class counts")
     ap.add_argument("--rows", type=int, default=1 << 20)
     ap.add_argument("--ceiling_rows", type=int, default=1 << 24)
     ap.add_argument("--out", default=None, help="also write the results as JSON")
@@ -205,7 +267,8 @@ def main(argv=None) -> int:
     res = {}
     for what in a.what.split(","):
         if what == "eval":
-            res[what] = bench_weighted(dev, a.rows) if a.weighted else bench_eval(dev, a.rows)
+            res[what] = (bench_many(dev, a.rows, a.features, [int(k) for k in a.classes.split(",")]) if a.many else bench_weighted(dev, a.rows) if a.weighted
+                         else bench_eval(dev, a.rows))
         elif what == "truth":
             res[what] = bench_truth(dev)
         elif what == "ceiling":
