@@ -22,6 +22,7 @@
 #include "../kernels/score_kernels.h"
 #include "../solver/fit.h"
 #include "../solver/fit_many.h"
+#include "../solver/wide_fit_many.h"
 #include "../solver/solver.h"
 #include "../solver/wide_fit.h"
 #include "../solver/wide_solver.h"
@@ -521,7 +522,59 @@ PYBIND11_MODULE(_psx_hip, m) {
             py::gil_scoped_release nogil;
             return f.stage_ms(raw ? 1 : 0, S(stream));
           },
-          py::arg("raw"), py::arg("stream") = 0);
+          py::arg("raw"), py::arg("stream") = 0)
+      // Many fits per read of the rows (csrc/solver/wide_fit_many.h), with the dense fitter's argument order.
+      // Vectors are in the full layout P = F*KP + KP: job m's weights -> w_out + m * P (the untouched features
+      // are the caller's), its sigma -> std_out + m * U.
+      .def_property_readonly("many_capacity", [](WideBatchFitter& f) { return wide_many_slots(f.padded_classes()); })
+      .def_property_readonly("many_round_seconds", [](WideBatchFitter& f) { return f.many().round_seconds(); })
+      .def(
+          "fit_many",
+          [](WideBatchFitter& f, uintptr_t sample_weight, const std::vector<float>& class_weight, uintptr_t fold,
+             const std::vector<double>& regs, const std::vector<int>& holdouts, const std::vector<uintptr_t>& w0s,
+             int max_iter, double tol, int ls_max, bool zero_const, uintptr_t w_out, uintptr_t std_out,
+             uintptr_t stream) {
+            if (!class_weight.empty() && (int)class_weight.size() != f.class_weights())
+              throw std::invalid_argument("fit_many: one class weight per class (two for the one-logit model)");
+            if (regs.size() != holdouts.size() || regs.size() != w0s.size())
+              throw std::invalid_argument("fit_many: one penalty, held-out fold and start per job");
+            std::vector<FitManyJob> jobs(regs.size());
+            for (size_t m = 0; m < jobs.size(); ++m) jobs[m] = {regs[m], holdouts[m], P<const float>(w0s[m])};
+            FitOpts o;
+            o.max_iter = max_iter;
+            o.tol = tol;
+            o.ls_max = ls_max;
+            o.zero_const = zero_const ? 1 : 0;
+            std::vector<FitManyResult> res;
+            {
+              py::gil_scoped_release nogil;
+              res = f.many().fit(P<const float>(sample_weight), class_weight.empty() ? nullptr : class_weight.data(),
+                                 P<const uint8_t>(fold), jobs, o, P<float>(w_out), P<float>(std_out), S(stream));
+            }
+            py::list out;
+            for (const auto& r : res)
+              out.append(py::make_tuple(r.objective, r.log_loss, r.history, r.accepted, r.evals, r.reason, r.ls_fail));
+            return out;
+          },
+          py::arg("sample_weight"), py::arg("class_weight"), py::arg("fold"), py::arg("regs"), py::arg("holdouts"),
+          py::arg("w0s"), py::arg("max_iter"), py::arg("tol"), py::arg("ls_max"), py::arg("zero_const"),
+          py::arg("w_out"), py::arg("std_out"), py::arg("stream") = 0)
+      .def(
+          "loss_grad_many",
+          [](WideBatchFitter& f, uintptr_t sample_weight, const std::vector<float>& class_weight, uintptr_t fold,
+             uintptr_t ws, const std::vector<int>& holdouts, uintptr_t grads, uintptr_t stream) {
+            if (!class_weight.empty() && (int)class_weight.size() != f.class_weights())
+              throw std::invalid_argument("loss_grad_many: one class weight per class (two for the one-logit model)");
+            std::vector<FitManyJob> jobs(holdouts.size());
+            for (size_t m = 0; m < jobs.size(); ++m)
+              jobs[m] = {0.0, holdouts[m], ws ? P<const float>(ws) + m * f.full_size() : nullptr};
+            std::vector<double> losses, ho;
+            f.many().loss_grad(P<const float>(sample_weight), class_weight.empty() ? nullptr : class_weight.data(),
+                               P<const uint8_t>(fold), jobs, P<float>(grads), losses, ho, S(stream));
+            return py::make_tuple(losses, ho);
+          },
+          py::arg("sample_weight"), py::arg("class_weight"), py::arg("fold"), py::arg("ws"), py::arg("holdouts"),
+          py::arg("grads"), py::arg("stream") = 0);
   m.attr("wide_fit_short") = kWideFitShort;
   m.attr("wide_fit_reduce_cap") = kWideReduceMaxWG * 256;  // elements of one trip of the wide reduction
   m.def(

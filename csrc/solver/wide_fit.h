@@ -13,6 +13,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include <memory>
 #include <vector>
 
 #include "../kernels/wide_fit_kernels.h"
@@ -20,6 +21,8 @@
 #include "fit_driver.h"
 
 namespace psx {
+
+class WideFitMany;
 
 class WideBatchFitter : public FitDriver {
  public:
@@ -48,6 +51,12 @@ class WideBatchFitter : public FitDriver {
   // of loss_grad (gradient only); raw = 0: the reduction of a fit's evaluation, which
   // also reads the solver's vectors for the 4 + 2 hist fp64 dots.
   std::vector<float> stage_ms(int raw, hipStream_t s);
+  // Many fits per read of the rows (wide_fit_many.h) on the resident dataset; its workspace
+  // is its own, made on first use and dropped by the next set_data.  It keeps its own row
+  // weights and statistics: set_weights and a fit in progress here are not disturbed.
+  WideFitMany& many();
+  int padded_classes() const { return dv_.KP; }
+  size_t full_size() const { return ((size_t)dv_.F + 1) * dv_.KP; }  // F*KP + KP of the loaded dataset's model
 
  protected:
   // the weights are the full layout [F*KP + KP]: begin gathers w0 through uniq, finalize
@@ -68,6 +77,7 @@ class WideBatchFitter : public FitDriver {
   WideFitWeightsDev wd_{};
   bool weighted_ = false;
   void* ws_ = nullptr;  // per-dataset workspace (every size depends on U, N or the items)
+  std::unique_ptr<WideFitMany> many_;
 };
 
 }  // namespace psx

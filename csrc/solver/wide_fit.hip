@@ -4,6 +4,7 @@
 #include <stdexcept>
 
 #include "solver.h"
+#include "wide_fit_many.h"
 
 namespace psx {
 
@@ -34,6 +35,7 @@ void WideBatchFitter::set_data(const WideFitData& d, hipStream_t s) {
       (d.n_short > 0 && !d.short_items) || (d.n_long > 0 && !d.long_items))
     throw std::invalid_argument("null dataset pointer");
   end_fit();
+  many_.reset();
   weighted_ = false;
   wd_ = WideFitWeightsDev{};
   wd_.holdout = -1;
@@ -173,6 +175,12 @@ std::vector<float> WideBatchFitter::stage_ms(int raw, hipStream_t s) {
   std::vector<float> ms(3);
   for (int i = 0; i < 3; ++i) hip_check(hipEventElapsedTime(&ms[i], t.ev[i], t.ev[i + 1]), "hipEventElapsedTime");
   return ms;
+}
+
+WideFitMany& WideBatchFitter::many() {
+  if (!ws_) throw std::runtime_error("fit_many: no dataset (set_data first)");
+  if (!many_) many_ = std::make_unique<WideFitMany>(dv_, G_);
+  return *many_;
 }
 
 void WideBatchFitter::read_std(float* std_out, hipStream_t s) {

@@ -15,7 +15,8 @@ without improvement).  ``--class_weight`` weighs the rows by their class (``bala
 N / (classes present * class count); with ``--sigmoid`` two weights, ``w0,w1``); ``--cv K --reg_params a,b,c`` runs a
 K-fold cross-validation of the penalties on the resident rows, prints its table to stderr
 and fits the whole set at the best one (it excludes ``--valid`` / ``--valid_frac``); ``--cv_batch auto|N``
-runs its fits N at a time on one read of the rows per evaluation (dense model, a class-weight table).
+runs its fits N at a time on one read of the rows per evaluation (dense or wide model, a class-weight table;
+``auto`` batches where that was measured faster and runs the fits one after another elsewhere).
 ``--checkpoint_dir`` gets a ``server.ckpt`` that
 ``python -m psx.apps.predict`` reads.  stdout gets one JSON line: rows, features,
 classes, iterations, evaluations, reason, objective, train log-loss, the test metrics
@@ -57,7 +58,7 @@ def fit_parser():
     ap.add_argument("--class_weight", default=None, help="'balanced' or one weight per class, w0,w1,... (--sigmoid: w0,w1)")
     ap.add_argument("--cv", type=int, default=0, help="folds of a cross-validation over --reg_params")
     ap.add_argument("--reg_params", default=None, help="penalties --cv compares, a,b,c")
-    ap.add_argument("--cv_batch", default=None, help="'auto' or N: fits of --cv that share one read of the rows")
+    ap.add_argument("--cv_batch", default=None, help="'auto' or N: fits of --cv that share one read of the rows (CSV and LIBSVM --train alike)")
     return ap
 
 

@@ -31,7 +31,10 @@ Many fits per read of the rows (:class:`FitJob`, :meth:`BatchFitter.fit_many`,
 weight streams and differ in the held-out fold, the penalty and the iterate, so one
 staged tile serves several of them -- ``csrc/kernels/fit_many.hip`` packs the models into
 the MFMA columns a single ``K``-class model leaves empty and ``csrc/solver/fit_many.hip``
-advances all fits in lockstep, one evaluation round at a time.
+advances all fits in lockstep, one evaluation round at a time.  The wide model
+(:class:`psx.ops.wide_fit.WideFitter`) has the same calls: ``csrc/kernels/wide_fit_many.hip``
+lays ``32 / KP`` models side by side in each feature's 128-byte line, so one gather, one
+read of the rows, of the inverted index and of the work items serves all of them.
 
 fp32 rows are converted to bf16, as :class:`psx.ops.score.Scorer` does: the fit sees
 the rounded features.
@@ -393,8 +396,6 @@ class _FitterBase:
     def _many_setup(self, ds, weights, holdouts, min_rows):
         """Checks of a batched call (ValueError before any launch) -> the checked weights of every distinct
         held-out fold, in the jobs' order."""
-        if isinstance(self.spec, WideSpec):
-            raise ValueError("fit_many / loss_grad_many serve the dense model (ModelSpec), not the wide one")
         weights = weights or FitWeights()
         if weights.holdout is not None:
             raise ValueError("the shared FitWeights of a batched call hold no fold out: every job names its own")
@@ -412,6 +413,16 @@ class _FitterBase:
         sw, fold = self._streams(data, wts)
         return data, (sw.data_ptr() if sw is not None else 0, wts.cw.tolist() if wts.cw is not None else [],
                       fold.data_ptr() if fold is not None else 0)
+
+    def _many_outputs(self, data, jobs):
+        """The device buffers a batched fit writes: weights ``[M, P]`` and sigmas ``[M, width]``."""
+        M, s = len(jobs), self.spec
+        return (torch.empty(M, s.P, dtype=torch.float32, device=self.device),  # finalize writes all of it
+                torch.empty(M, s.Fp, dtype=torch.float32, device=self.device))
+
+    def _many_std_features(self, data, std_m):
+        """``FitResult.std`` / ``features`` of one job from its row of the sigma buffer."""
+        return std_m[: self.spec.F].clone(), None
 
     def loss_grad_many(self, ds, ws, weights: FitWeights | None, holdouts):
         """One raw evaluation of the M weight vectors ``ws`` (``[M, P]``, device layout; no standardisation,
@@ -437,7 +448,8 @@ class _FitterBase:
 
     @property
     def many_capacity(self) -> int:
-        """Models one read of the rows serves on the GPU: a function of the padded width and the class count."""
+        """Models one read of the rows serves on the GPU: a function of the padded width and the class count
+        (dense), of the padded class count alone (wide: ``32 // KP``)."""
         return int(self._native.many_capacity)
 
     def fit_many(self, train, jobs, weights: FitWeights | None = None) -> list:
@@ -466,12 +478,11 @@ class _FitterBase:
         t0 = time.perf_counter()
         with torch.cuda.device(self.device):
             st, nat, M = stream_handle(self.device), self._native, len(jobs)
-            _, streams = self._many_resident(train, checked[0])
+            data, streams = self._many_resident(train, checked[0])
             w0s = [None if j.w0 is None else j.w0.detach().to(self.device, torch.float32).reshape(-1).contiguous()
                    for j in jobs]
             holds = [-1 if j.holdout is None else int(j.holdout) for j in jobs]
-            w = torch.empty(M, s.P, dtype=torch.float32, device=self.device)
-            std = torch.empty(M, s.Fp, dtype=torch.float32, device=self.device)
+            w, std = self._many_outputs(data, jobs)
             rows = nat.fit_many(*streams, [float(j.reg_param) for j in jobs], holds,
                                 [0 if t is None else t.data_ptr() for t in w0s], int(o.max_iter), float(o.tol),
                                 int(o.ls_max), bool(o.zero_const), w.data_ptr(), std.data_ptr(), st)
@@ -480,12 +491,15 @@ class _FitterBase:
             if any(h >= 0 for h in holds):  # one more round: every job's held-out loss at its returned weights
                 ho = nat.loss_grad_many(*streams, w.data_ptr(), holds, torch.empty_like(w).data_ptr(), st)[1]
         dt = time.perf_counter() - t0
-        return [FitResult(spec=s, w=w[m].clone(), objective=float(r[0]), log_loss=float(r[1]), history=list(r[2]),
-                          iters=int(r[3]), evals=int(r[4]), reason=str(r[5]), std=std[m, : s.F].clone(), seconds=dt,
-                          pass_seconds=statistics.median(ev) if ev else 0.0,
-                          options=replace(o, reg_param=float(jobs[m].reg_param)), ls_fail=int(r[6]),
-                          holdout_log_loss=float(ho[m]) if holds[m] >= 0 else None)
-                for m, r in enumerate(rows)]
+        out = []
+        for m, r in enumerate(rows):
+            sd, features = self._many_std_features(data, std[m])
+            out.append(FitResult(spec=s, w=w[m].clone(), objective=float(r[0]), log_loss=float(r[1]), history=list(r[2]),
+                                 iters=int(r[3]), evals=int(r[4]), reason=str(r[5]), std=sd, seconds=dt,
+                                 pass_seconds=statistics.median(ev) if ev else 0.0,
+                                 options=replace(o, reg_param=float(jobs[m].reg_param)), ls_fail=int(r[6]),
+                                 features=features, holdout_log_loss=float(ho[m]) if holds[m] >= 0 else None))
+        return out
 
     # ---- the fit ---------------------------------------------------------------
     def fit(self, train, w0: torch.Tensor | None = None, valid=None, valid_every: int = 1,
@@ -646,6 +660,13 @@ def loss_grad(spec: ModelSpec, ds: Dataset, w: torch.Tensor, device, max_wg: int
     return BatchFitter(spec, device, FitOptions(max_wg=max_wg)).loss_grad(ds, w)
 
 
+# Padded class counts at which ``cross_validate(batch="auto")`` batches the wide model: those where the batched
+# grid was MEASURED faster than the sequential one.  2^20 rows x 45 entries in 2^20 features, 5 folds x 4 penalties
+# (profiles/r21/README.md): batched / sequential 0.353 / 0.853 s with one logit (KP 1), 0.597 / 1.165 s with 6
+# classes (KP 8).  KP 2, 4 and 16 have not been measured: "auto" takes the sequential path there.
+WIDE_AUTO_BATCH_KP = (1, 8)
+
+
 @dataclass
 class CVResult:
     reg_params: list
@@ -668,10 +689,11 @@ def cross_validate(spec, ds, reg_params, folds: int = 5, seed: int = 0, device="
     while it runs: every fit reuses the first one's resident copies (see :class:`FitWeights`).
 
     ``batch``: None runs the fits one after another.  A number runs them that many at a time through
-    :meth:`BatchFitter.fit_many` (one read of the rows per evaluation round and ``many_capacity`` jobs),
-    ``"auto"`` all of them at once -- or one after another where a read of the rows serves a single
-    model (``many_capacity`` 1).  Dense model, a class-weight table or none; the held-out losses agree with
-    the sequential path to the fits' accuracy, not bit for bit."""
+    ``fit_many`` of the dense or the wide fitter (one read of the rows per evaluation round and
+    ``many_capacity`` jobs), ``"auto"`` all of them at once -- or one after another where that is not
+    faster: a dense model whose read of the rows serves a single model (``many_capacity`` 1), and the wide
+    model at the padded class counts of ``WIDE_AUTO_BATCH_KP`` only.  A class-weight table or none; the
+    held-out losses agree with the sequential path to the fits' accuracy, not bit for bit."""
     regs = [float(r) for r in reg_params]
     if not regs or not 2 <= folds <= 255 or folds > ds.rows:
         raise ValueError("cross_validate needs penalties and 2 <= folds <= min(255, rows)")
@@ -687,13 +709,15 @@ def cross_validate(spec, ds, reg_params, folds: int = 5, seed: int = 0, device="
         f = WideFitter(spec, device, o, col_chunk=col_chunk)
     else:
         f = BatchFitter(spec, device, o)
-    if batch is not None and (isinstance(spec, WideSpec) or not (batch == "auto" or (isinstance(batch, int) and batch >= 1))):
-        raise ValueError("cross_validate(batch=...) is 'auto' or a number >= 1 and serves the dense model")
+    if batch is not None and not (batch == "auto" or (isinstance(batch, int) and batch >= 1)):
+        raise ValueError("cross_validate(batch=...) is 'auto' or a number >= 1")
     # "auto": batched wherever one read of the rows serves at least two models.  Measured on 2^20 rows, 5 folds x
     # 4 penalties (profiles/r20/README.md): batched / sequential 0.174 / 0.352 s at width 1,024 with 6 classes,
     # 0.045 / 0.152 s with 2, and faster in every other measured cell (widths 128, 512, 2,048; 2 and 6 classes).
     # With capacity 1 (width 2,048, more than 8 classes) there is nothing to share: the sequential path.
     if batch == "auto" and f._native is not None and f.many_capacity < 2:
+        batch = None
+    if batch == "auto" and f._native is not None and isinstance(spec, WideSpec) and spec.KP not in WIDE_AUTO_BATCH_KP:
         batch = None
     if batch is not None:
         jobs = [FitJob(r, k) for r in regs for k in range(folds)]

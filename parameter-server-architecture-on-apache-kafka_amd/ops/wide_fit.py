@@ -26,6 +26,12 @@ rows' weights and one statistics pass -- :func:`psx.ops.fit.cross_validate` choo
 feature that takes one value on the rows of positive training weight (absent = 0), one
 only held-out or zero-weight rows touch included, is excluded like a constant one.
 
+Many fits per read of the rows (:class:`psx.ops.fit.FitJob`, :meth:`WideFitter.fit_many`,
+:meth:`WideFitter.loss_grad_many`, ``cross_validate(batch=...)``):
+``csrc/kernels/wide_fit_many.hip`` driven by ``csrc/solver/wide_fit_many.hip``.
+``many_capacity = 32 // KP`` models lie side by side in each feature's 128-byte line; every
+result's ``std`` / ``features`` are what :meth:`WideFitter.fit` returns.
+
 CPU: :func:`psx.models.reference.fit_reference` on float64 sparse closures (the CSR
 matrix over the touched columns and its transpose); no ``N x F`` matrix is built.
 """
@@ -33,6 +39,7 @@ from __future__ import annotations
 
 import time
 import warnings
+from dataclasses import replace
 
 import torch
 
@@ -269,6 +276,20 @@ class WideFitter(_FitterBase):
         std = torch.empty(d.U, dtype=torch.float32, device=self.device)
         self._native.read_std(std.data_ptr(), st)
         return std, d.uniq.clone()
+
+    def _many_outputs(self, d, jobs):
+        o = self.opts
+        try:  # every job's untouched features under its own penalty (centred when it is 0)
+            ws = []
+            for j in jobs:
+                self.opts = replace(o, reg_param=float(j.reg_param))
+                ws.append(self._untouched(j.w0))
+        finally:
+            self.opts = o
+        return torch.stack(ws), torch.empty(len(jobs), max(d.U, 1), dtype=torch.float32, device=self.device)
+
+    def _many_std_features(self, d, std_m):
+        return std_m[: d.U].clone(), d.uniq.clone()
 
     def _loss_grad_cpu(self, ds, w, resident):
         s = self.spec

@@ -18,7 +18,13 @@
            events around set_weights); and, with --cv FOLDS, the wall time of a
            FOLDS x 3-penalty cross_validate of 10 iterations a fit.
 
-Usage: python tools/bench_wide_fit.py [--what eval,chunk,setup,fit | --weights [--cv 5]] [--rows N] [--out FILE.json]
+  --many   (instead of --what) many fits per read of the rows (csrc/kernels/wide_fit_many.hip): one raw
+           evaluation of 1, slots / 2 and slots models (the round of loss_grad_many: all passes, the
+           reductions, the copy of the result blocks and the wait) against that many plain weighted
+           evaluations (device events around the three stages), alternating inside every repeat; and a
+           5-fold x 4-penalty cross_validate of 10 iterations a fit, batched against sequential, alternating.
+
+Usage: python tools/bench_wide_fit.py [--what eval,chunk,setup,fit | --weights [--cv 5] | --many] [--rows N] [--out FILE.json]
 """
 from __future__ import annotations
 
@@ -211,6 +217,44 @@ def bench_weights(dev, rows, K, repeats, cv_folds):
     return out
 
 
+def bench_many(dev, rows, K, repeats):
+    spec = WideSpec(F, K)
+    ds = _data(dev, rows, K)
+    g = torch.Generator().manual_seed(0)
+    shared = FitWeights(torch.rand(rows, generator=g) * 2, 0.5 + torch.rand(max(K, 2), generator=g),
+                        torch.randint(0, 5, (rows,), generator=g).to(torch.uint8))
+    fitter = WideFitter(spec, dev)
+    st, nat = stream_handle(dev), fitter._native
+    slots = fitter.many_capacity
+    one = FitWeights(shared.sample_weight, shared.class_weight, shared.fold, 0)
+    w = spec.init("random", seed=1, scale=0.05).to(dev)
+    fitter.loss_grad(ds, w, weights=one)  # loads the dataset, applies the weights, warms up
+    out = {"rows": rows, "K": K, "KP": spec.KP, "slots": slots, "eval": []}
+    for M in sorted({1, max(1, slots // 2), slots}):
+        ws = w.repeat(M, 1)
+        holds = [m % 5 for m in range(M)]
+        fitter.loss_grad_many(ds, ws, shared, holds)
+        many, plain = [], []
+        for _ in range(repeats):
+            fitter.loss_grad_many(ds, ws, shared, holds)
+            many.append(nat.many_round_seconds[0] * 1e3)
+            plain.append(M * sum(nat.stage_ms(True, st)))
+        out["eval"].append({"models": M, "many_ms": _med(many), "plain_ms": _med(plain),
+                            "many_spread_ms": max(many) - min(many)})
+        del ws
+    regs, kw = [1e-4, 1e-3, 1e-2, 1e-1], dict(folds=5, device=dev, opts=FitOptions(max_iter=10))
+    cross_validate(spec, ds, regs[:1], batch=5, **kw)  # warm-up of both paths' first touches
+    seq, bat = [], []
+    for _ in range(max(1, repeats // 2)):
+        seq.append(cross_validate(spec, ds, regs, **kw))
+        bat.append(cross_validate(spec, ds, regs, batch=20, **kw))
+    out.update(cv_sequential_s=_med([c.seconds for c in seq]), cv_batched_s=_med([c.seconds for c in bat]),
+               cv_best=(seq[0].best_reg_param, bat[0].best_reg_param),
+               cv_loss_gap=max(abs(a - b) for a, b in zip(sum(seq[0].losses, []), sum(bat[0].losses, []))))
+    print(json.dumps(out))
+    return out
+
+
 def main(argv=None) -> int:
     ap = argparse.ArgumentParser()
     ap.add_argument("--what", default="eval,chunk,setup,fit")
@@ -219,6 +263,8 @@ def main(argv=None) -> int:
     ap.add_argument("--out", default=None, help="also write the results as JSON")
     ap.add_argument("--weights", action="store_true", help="the weighted evaluation against the plain one")
     ap.add_argument("--cv", type=int, default=0, help="with --weights: folds of a timed cross_validate")
+    ap.add_argument("--many", action="store_true", help="many fits per read of the rows against the plain evaluations")
+    ap.add_argument("--classes", default="6,1", help="with --many: class counts to measure")
     a = ap.parse_args(argv)
     if not torch.cuda.is_available():
         print("bench_wide_fit: no GPU -- not measured", file=sys.stderr)
@@ -226,6 +272,12 @@ def main(argv=None) -> int:
     dev = torch.device("cuda:0")
     print(f"default col_chunk {DEFAULT_COL_CHUNK}")
     res = {}
+    if a.many:
+        res["many"] = [bench_many(dev, a.rows, int(K), a.repeats) for K in a.classes.split(",")]
+        if a.out:
+            with open(a.out, "w") as f:
+                json.dump(res, f, indent=1)
+        return 0
     if a.weights:
         res["weights"] = [bench_weights(dev, a.rows, K, a.repeats, a.cv) for K in (6, 1)]
         if a.out:
