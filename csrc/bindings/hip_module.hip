@@ -22,6 +22,7 @@
 #include "../kernels/score_kernels.h"
 #include "../solver/fit.h"
 #include "../solver/fit_many.h"
+#include "../solver/panel_fit.h"
 #include "../solver/wide_fit_many.h"
 #include "../solver/solver.h"
 #include "../solver/wide_fit.h"
@@ -463,6 +464,37 @@ PYBIND11_MODULE(_psx_hip, m) {
           },
           py::arg("sample_weight"), py::arg("class_weight"), py::arg("fold"), py::arg("ws"), py::arg("holdouts"),
           py::arg("grads"), py::arg("stream") = 0);
+  // The panel family (psx/ops/panel_fit.py): dense rows of 2,048 < F <= 16,384 features.
+  py::class_<PanelBatchFitter, FitDriver>(m, "PanelBatchFitter")
+      .def(py::init<int, int, int, int, int>(), py::arg("K"), py::arg("F"), py::arg("FP"), py::arg("hist") = 10,
+           py::arg("max_wg") = 0)
+      .def(
+          "set_data",
+          [](PanelBatchFitter& f, uintptr_t X, uintptr_t y, int64_t N, int64_t Npad, bool stats, uintptr_t stream) {
+            f.set_data(P<const uint16_t>(X), P<const int32_t>(y), N, Npad, stats, S(stream));
+          },
+          py::arg("X"), py::arg("y"), py::arg("N"), py::arg("Npad"), py::arg("stats") = true, py::arg("stream") = 0)
+      .def(
+          "read_std",
+          [](PanelBatchFitter& f, uintptr_t out, uintptr_t stream) { f.read_std(P<float>(out), S(stream)); },
+          py::arg("out"), py::arg("stream") = 0)
+      // Row outputs [N] of the resident rows under the weights w; conf [256] and oor [1] are accumulated.
+      .def(
+          "score",
+          [](PanelBatchFitter& f, uintptr_t w, uintptr_t pred, uintptr_t proba, uintptr_t nll, uintptr_t conf,
+             uintptr_t oor, uintptr_t stream) {
+            const ScoreOut o{P<int32_t>(pred), P<float>(proba), P<float>(nll), P<int>(conf), P<int>(oor), nullptr};
+            f.score(P<const float>(w), o, S(stream));
+          },
+          py::arg("w"), py::arg("pred"), py::arg("proba") = 0, py::arg("nll") = 0, py::arg("conf") = 0,
+          py::arg("oor") = 0, py::arg("stream") = 0)
+      .def(
+          "time_launches",
+          [](PanelBatchFitter& f, uintptr_t w, int reps, uintptr_t stream) {
+            return f.time_launches(P<const float>(w), reps, S(stream));
+          },
+          py::arg("w"), py::arg("reps") = 5, py::arg("stream") = 0)
+      .def_property_readonly("weighted", [](PanelBatchFitter&) { return false; });  // (no row weights)
   py::class_<WideBatchFitter, FitDriver>(m, "WideBatchFitter")
       .def(py::init<int, int, int, int>(), py::arg("K"), py::arg("KP"), py::arg("hist") = 10, py::arg("max_wg") = 0)
       .def(

@@ -694,6 +694,10 @@ def cross_validate(spec, ds, reg_params, folds: int = 5, seed: int = 0, device="
     faster: a dense model whose read of the rows serves a single model (``many_capacity`` 1), and the wide
     model at the padded class counts of ``WIDE_AUTO_BATCH_KP`` only.  A class-weight table or none; the
     held-out losses agree with the sequential path to the fits' accuracy, not bit for bit."""
+    from .panel_fit import PanelSpec  # (imports this module)
+
+    if isinstance(spec, PanelSpec):
+        raise NotImplementedError("cross_validate is not implemented for the panel model")
     regs = [float(r) for r in reg_params]
     if not regs or not 2 <= folds <= 255 or folds > ds.rows:
         raise ValueError("cross_validate needs penalties and 2 <= folds <= min(255, rows)")
