@@ -22,6 +22,7 @@
 #include "../kernels/score_kernels.h"
 #include "../solver/fit.h"
 #include "../solver/fit_many.h"
+#include "../solver/fit_f32.h"
 #include "../solver/panel_fit.h"
 #include "../solver/wide_fit_many.h"
 #include "../solver/solver.h"
@@ -495,6 +496,36 @@ PYBIND11_MODULE(_psx_hip, m) {
           },
           py::arg("w"), py::arg("reps") = 5, py::arg("stream") = 0)
       .def_property_readonly("weighted", [](PanelBatchFitter&) { return false; });  // (no row weights)
+  // The fp32-row family (psx/ops/fit_f32.py): dense rows kept in fp32, padded widths up to 1,024.
+  py::class_<F32BatchFitter, FitDriver>(m, "F32BatchFitter")
+      .def(py::init<int, int, int, int, int>(), py::arg("K"), py::arg("F"), py::arg("FP"), py::arg("hist") = 10,
+           py::arg("max_wg") = 0)
+      .def(
+          "set_data",
+          [](F32BatchFitter& f, uintptr_t X, uintptr_t y, int64_t N, int64_t Npad, bool stats, uintptr_t stream) {
+            f.set_data(P<const float>(X), P<const int32_t>(y), N, Npad, stats, S(stream));
+          },
+          py::arg("X"), py::arg("y"), py::arg("N"), py::arg("Npad"), py::arg("stats") = true, py::arg("stream") = 0)
+      .def(
+          "read_std", [](F32BatchFitter& f, uintptr_t out, uintptr_t stream) { f.read_std(P<float>(out), S(stream)); },
+          py::arg("out"), py::arg("stream") = 0)
+      // Row outputs [N] of the resident rows under the weights w; conf [256] and oor [1] are accumulated.
+      .def(
+          "score",
+          [](F32BatchFitter& f, uintptr_t w, uintptr_t pred, uintptr_t proba, uintptr_t nll, uintptr_t conf,
+             uintptr_t oor, uintptr_t stream) {
+            const ScoreOut o{P<int32_t>(pred), P<float>(proba), P<float>(nll), P<int>(conf), P<int>(oor), nullptr};
+            f.score(P<const float>(w), o, S(stream));
+          },
+          py::arg("w"), py::arg("pred"), py::arg("proba") = 0, py::arg("nll") = 0, py::arg("conf") = 0,
+          py::arg("oor") = 0, py::arg("stream") = 0)
+      .def(
+          "time_launches",
+          [](F32BatchFitter& f, uintptr_t w, int reps, uintptr_t stream) {
+            return f.time_launches(P<const float>(w), reps, S(stream));
+          },
+          py::arg("w"), py::arg("reps") = 5, py::arg("stream") = 0)
+      .def_property_readonly("weighted", [](F32BatchFitter&) { return false; });  // (no row weights)
   py::class_<WideBatchFitter, FitDriver>(m, "WideBatchFitter")
       .def(py::init<int, int, int, int>(), py::arg("K"), py::arg("KP"), py::arg("hist") = 10, py::arg("max_wg") = 0)
       .def(

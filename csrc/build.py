@@ -87,7 +87,7 @@ def _local_includes(src):
 NO_PACKED_FP32 = ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"]
 EXTRA_CFLAGS = {"fit_weighted.hip": NO_PACKED_FP32, "wide_fit_weighted.hip": NO_PACKED_FP32,
                 "fit_many.hip": NO_PACKED_FP32, "wide_fit_many.hip": NO_PACKED_FP32,
-                "panel_fit.hip": NO_PACKED_FP32}  # (both files of either name)
+                "panel_fit.hip": NO_PACKED_FP32, "fit_f32.hip": NO_PACKED_FP32}  # (both files of either name)
 
 
 def _compile_link(compiler, sources, out, cflags, ldflags, jobs, objdir, headers=()):
