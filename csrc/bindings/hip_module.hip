@@ -498,14 +498,31 @@ PYBIND11_MODULE(_psx_hip, m) {
       .def_property_readonly("weighted", [](PanelBatchFitter&) { return false; });  // (no row weights)
   // The fp32-row family (psx/ops/fit_f32.py): dense rows kept in fp32, padded widths up to 1,024.
   py::class_<F32BatchFitter, FitDriver>(m, "F32BatchFitter")
-      .def(py::init<int, int, int, int, int>(), py::arg("K"), py::arg("F"), py::arg("FP"), py::arg("hist") = 10,
-           py::arg("max_wg") = 0)
+      .def(py::init<int, int, int, int, int, bool>(), py::arg("K"), py::arg("F"), py::arg("FP"), py::arg("hist") = 10,
+           py::arg("max_wg") = 0, py::arg("centred") = false)
       .def(
           "set_data",
           [](F32BatchFitter& f, uintptr_t X, uintptr_t y, int64_t N, int64_t Npad, bool stats, uintptr_t stream) {
             f.set_data(P<const float>(X), P<const int32_t>(y), N, Npad, stats, S(stream));
           },
           py::arg("X"), py::arg("y"), py::arg("N"), py::arg("Npad"), py::arg("stats") = true, py::arg("stream") = 0)
+      // The centred mode (x - c in every kernel): the centre [FP] of a dataset loaded without statistics, the
+      // centre in use, and one evaluation whose gradient stays in centred coordinates.
+      .def(
+          "set_center",
+          [](F32BatchFitter& f, uintptr_t c, uintptr_t stream) { f.set_center(P<const float>(c), S(stream)); },
+          py::arg("c"), py::arg("stream") = 0)
+      .def(
+          "read_center",
+          [](F32BatchFitter& f, uintptr_t out, uintptr_t stream) { f.read_center(P<float>(out), S(stream)); },
+          py::arg("out"), py::arg("stream") = 0)
+      .def_property_readonly("centred", &F32BatchFitter::centred)
+      .def(
+          "loss_grad_centred",
+          [](F32BatchFitter& f, uintptr_t w, uintptr_t grad, uintptr_t stream) {
+            return f.loss_grad_centred(P<const float>(w), P<float>(grad), S(stream));
+          },
+          py::arg("w"), py::arg("grad"), py::arg("stream") = 0)
       .def(
           "read_std", [](F32BatchFitter& f, uintptr_t out, uintptr_t stream) { f.read_std(P<float>(out), S(stream)); },
           py::arg("out"), py::arg("stream") = 0)

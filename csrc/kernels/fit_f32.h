@@ -36,16 +36,26 @@ constexpr int fit_f32_wg_per_cu(int FP) {
 struct F32Dev {
   const float* X;  // [Npad][FP] fp32, rows >= N and columns >= F zero
   float* mmpart;   // [G][2][FP] per-workgroup column minimum / maximum over the rows < N
+  float* center;   // [FP] c_f: the column's mean, a constant column's value itself, 0 for padding features
 };
 
 void prepare_fit_f32_kernels();
-// sigma / 1/sigma of every feature over the N rows, every element widened to double
-// (G workgroups, then one fixed-order pass); a column is constant iff its max == min
+// sigma / 1/sigma and the centre c of every feature over the N rows, every element widened
+// to double (G workgroups, then one fixed-order pass); a column is constant iff its max == min
 void launch_fit_stats_f32(const FitDev& dv, const F32Dev& fd, int G, hipStream_t s);
 // loss partials, residual sums and the [G][K][FP] gradient partials at the trial fragments
-// (one launch); launch_fit_reduce follows unchanged
-void launch_fit_lossgrad_f32(const FitDev& dv, const F32Dev& fd, int G, hipStream_t s);
+// (one launch); launch_fit_reduce follows unchanged.  centred: on the rows x - c
+void launch_fit_lossgrad_f32(const FitDev& dv, const F32Dev& fd, int G, bool centred, hipStream_t s);
 // the row outputs of score_kernels.h at the trial fragments (labels required, no histogram)
-void launch_score_f32(const FitDev& dv, const F32Dev& fd, int G, const ScoreOut& o, hipStream_t s);
+void launch_score_f32(const FitDev& dv, const F32Dev& fd, int G, bool centred, const ScoreOut& o, hipStream_t s);
+
+// The centred mode's three vector kernels: fp64, one workgroup, a fixed summation order.
+// After launch_fit_begin (same w0 and raw): b'_k = b_k + sum_f c_f w_eff[k][f] -> b_eff, and,
+// in a fit (raw == 0), the optimiser's intercept entries of x and beta_t.
+void launch_fit_center_begin(const FitDev& dv, const F32Dev& fd, const float* w0, int raw, hipStream_t s);
+// After launch_fit_finalize: w_out's intercepts = b'_k - sum_f c_f w_out[k][f], centred over the classes.
+void launch_fit_center_finalize(const FitDev& dv, const F32Dev& fd, float* w_out, hipStream_t s);
+// The last evaluation's gradient in raw coordinates: grad[k][f] = g_t[k][f] + c_f g_t[b_k], intercepts copied.
+void launch_fit_center_grad(const FitDev& dv, const F32Dev& fd, float* grad, hipStream_t s);
 
 }  // namespace psx

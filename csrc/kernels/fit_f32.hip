@@ -32,6 +32,14 @@
 //                       never winning; labels clamped for the confusion cell; NaN loss and
 //                       *oor for a label outside [0, K)); integer atomics only.
 //
+//   <FP, true>          the centred instantiations of the two kernels above: the same bodies
+//                       over stage_tile_f32c, which subtracts the column's centre c_f in fp32
+//                       before the split.  A column at 100 +- 1 then spends the 16 bits of
+//                       hi + lo on its variation, and the optimiser sees a problem whose
+//                       conditioning does not grow with (mean / sigma)^2.  The statistics
+//                       pass writes c; three one-line fp64 vector kernels map the intercepts
+//                       (b' = b + sum_f c_f w_f) and the gradient between the coordinates.
+//
 // LDS per workgroup: fit_f32_lds_bytes(FP) = two images + the 11.75 KB tail: 142,848 B at
 // 1,024 (one workgroup per CU), 77,312 at 512 (two), 44,544 at 256, 28,160 at 128.
 // Every sum runs in a fixed order (waves in order, butterflies, workgroups in order in
@@ -69,14 +77,76 @@ struct F32Lds {
 };
 static_assert(8192 + 2048 + (32 + 64 + 4) * 4 <= 8192 + 2048 + 1024 + 512, "the tail of eval_lds_bytes");
 
+// Centred mode.  stage_tile_f32 (tile.h) with x - c_f formed in fp32 before the split, so the
+// 16 bits of hi + lo are spent on the column's variation and not on its magnitude.  Thread t
+// stages the chunks q = t + 256 j and 256 is a multiple of CPR = FP / 8, so its column group
+// q % CPR = t % CPR is the same for every chunk of every tile: it needs 8 centre values, ever.
+// A padding row (zeros) stages as -c; its residual is 0 and its outputs are never written.
+template <int FP>
+__device__ __forceinline__ void stage_tile_f32c(char* lds_hi, char* lds_lo, const float* __restrict__ X, int64_t row0,
+                                                const f32x4 c0, const f32x4 c1) {
+  constexpr int CPR = FP / 8;            // 8-feature chunks per row
+  constexpr int PER_T = 32 * CPR / 256;  // chunks per thread
+  constexpr int BATCH = PER_T < 8 ? PER_T : 8;
+  static_assert(256 % CPR == 0, "a thread's column group does not depend on the chunk");
+  const int cg = threadIdx.x % CPR, rbase = threadIdx.x / CPR;
+#pragma unroll
+  for (int b0 = 0; b0 < PER_T; b0 += BATCH) {
+    f32x4 v[BATCH][2];
+#pragma unroll
+    for (int j = 0; j < BATCH; ++j) {
+      const int row = rbase + (256 / CPR) * (b0 + j);
+      const float* src = X + (row0 + row) * FP + cg * 8;
+      v[j][0] = *(const f32x4*)src;
+      v[j][1] = *(const f32x4*)(src + 4);
+    }
+#pragma unroll
+    for (int j = 0; j < BATCH; ++j) {
+      const int row = rbase + (256 / CPR) * (b0 + j);
+      u16x8 h, l;
+#pragma unroll
+      for (int e = 0; e < 8; ++e) {
+        unsigned short hh, ll;
+        split_bf16(v[j][e >> 2][e & 3] - (e < 4 ? c0[e & 3] : c1[e & 3]), hh, ll);
+        h[e] = hh;
+        l[e] = ll;
+      }
+      const int o = (cg >> 4) * 8192 + lds_off(row, cg & 15);
+      *(u16x8*)(lds_hi + o) = h;
+      *(u16x8*)(lds_lo + o) = l;
+    }
+  }
+}
+
+// The staging thread's 8 centre values: fetched once per workgroup, beside the weight
+// fragments, and held in registers at every width (0 B of scratch, profiles/r24/README.md).
+template <int FP, bool kCenter>
+struct Center {
+  __device__ __forceinline__ explicit Center(const float*) {}
+};
+template <int FP>
+struct Center<FP, true> {
+  f32x4 c0, c1;
+  __device__ __forceinline__ explicit Center(const float* __restrict__ c) {
+    const float* src = c + (threadIdx.x % (FP / 8)) * 8;
+    c0 = *(const f32x4*)src;
+    c1 = *(const f32x4*)(src + 4);
+  }
+};
+
 // One read of the tile's fp32 rows into the two images and both forwards; the partial
 // logits of the four waves are in L.red after the barrier.
-template <int FP>
+template <int FP, bool kCenter>
 __device__ __forceinline__ void stage_and_forward(const F32Lds<FP>& L, const float* __restrict__ X,
-                                                  const int32_t* __restrict__ y, int64_t row0, const WFrag<FP>& wf) {
+                                                  const int32_t* __restrict__ y, int64_t row0, const WFrag<FP>& wf,
+                                                  const Center<FP, kCenter>& cen) {
   const int tid = threadIdx.x;
   const int yv = tid < 32 ? y[row0 + tid] : 0;  // issued with the tile's loads (one round trip)
-  stage_tile_f32<FP>(L.hi, L.lo, X, row0);
+  if constexpr (kCenter) {
+    stage_tile_f32c<FP>(L.hi, L.lo, X, row0, cen.c0, cen.c1);
+  } else {
+    stage_tile_f32<FP>(L.hi, L.lo, X, row0);
+  }
   if (tid < 32) L.ylab[tid] = yv;
   __syncthreads();
   f32x4 a0, a1;
@@ -89,7 +159,7 @@ __device__ __forceinline__ void stage_and_forward(const F32Lds<FP>& L, const flo
 }  // namespace
 
 // ---------------------------------------------------------------------------
-template <int FP>
+template <int FP, bool kCenter = false>
 __global__ __launch_bounds__(256) void fit_lossgrad_f32_kernel(FitDev dv, F32Dev fd) {
   extern __shared__ __attribute__((aligned(16))) char lds[];
   const F32Lds<FP> L(lds);
@@ -102,6 +172,7 @@ __global__ __launch_bounds__(256) void fit_lossgrad_f32_kernel(FitDev dv, F32Dev
   const bool v0 = sc0 < K, v1 = sc0 + 1 < K;
   WFrag<FP> wf;  // the trial weights do not depend on the tile: their latency overlaps the first staging
   load_wfrag<FP>(wf, dv.whi, dv.wlo, K);
+  const Center<FP, kCenter> cen(fd.center);
   const float bz0 = dv.b_eff[sc0], bz1 = dv.b_eff[sc0 + 1];
   f32x4 acc[NT];
 #pragma unroll
@@ -109,7 +180,7 @@ __global__ __launch_bounds__(256) void fit_lossgrad_f32_kernel(FitDev dv, F32Dev
   float loss = 0.f, rs0 = 0.f, rs1 = 0.f;
   for (int tile = g; tile < ntiles; tile += G) {
     const int64_t row0 = (int64_t)tile * 32;
-    stage_and_forward<FP>(L, fd.X, dv.y, row0, wf);
+    stage_and_forward<FP, kCenter>(L, fd.X, dv.y, row0, wf, cen);
     {  // softmax + cross entropy: 8 threads per row, 2 classes each
       const float z0 = v0 ? load_logit(L.red, sr, sc0) + bz0 : -INFINITY;
       const float z1 = v1 ? load_logit(L.red, sr, sc0 + 1) + bz1 : -INFINITY;
@@ -266,12 +337,90 @@ __global__ __launch_bounds__(256) void fit_stats_f32_fin_kernel(FitDev dv, F32De
   }
   dv.std_[f] = (float)sd;
   dv.inv_std[f] = sd > 0.0 ? (float)(1.0 / sd) : 0.f;
+  // the centre: the mean; a constant column's own value, so that it stages to exactly 0 (one
+  // row makes every column constant); 0 for padding features
+  fd.center[f] = f < dv.F ? (mx > mn ? (float)(a / n) : mn) : 0.f;
+}
+
+// ---------------------------------------------------------------------------
+// The centred mode's vector kernels.  Centring by any constant c is a reparametrisation,
+// z = (x - c) w + b' with b' = b + sum_f c_f w_f: the optimiser runs in (beta, b') and these
+// map the intercepts and the gradient between the two.  One workgroup, fp64, and a fixed
+// order: thread t sums the features t, t + 256, ... in order, then a tree over the threads.
+__device__ __forceinline__ double center_block_sum(double v, double* red) {
+  const int t = threadIdx.x;
+  __syncthreads();  // the previous sum's readers are done
+  red[t] = v;
+  __syncthreads();
+  for (int h = 128; h > 0; h >>= 1) {
+    if (t < h) red[t] += red[t + h];
+    __syncthreads();
+  }
+  return red[0];
+}
+
+// w_eff is the raw coefficient fit_begin_kernel / fit_write_trial wrote the fragments from.
+__global__ __launch_bounds__(256) void fit_center_begin_kernel(FitDev dv, F32Dev fd, const float* w0, int raw) {
+  __shared__ double red[256];
+  const int t = threadIdx.x, FP = dv.FP, KF = dv.K * dv.FP;
+  for (int k = 0; k < dv.K; ++k) {
+    double a = 0.0;
+    for (int f = t; f < dv.F; f += 256) {
+      const int e = k * FP + f;
+      float we;
+      if (raw) {
+        we = w0 ? w0[e] : 0.f;
+      } else {
+        const float iv = dv.inv_std[f];
+        we = iv > 0.f ? dv.x[e] * iv : dv.wfix[e];
+      }
+      a += (double)fd.center[f] * (double)we;
+    }
+    a = center_block_sum(a, red);
+    if (t == 0) {
+      const float bp = (float)((double)(raw ? (w0 ? w0[KF + k] : 0.f) : dv.x[KF + k]) + a);
+      dv.b_eff[k] = bp;
+      if (!raw) {
+        dv.x[KF + k] = bp;
+        dv.beta_t[KF + k] = bp;
+      }
+    }
+  }
+}
+
+__global__ __launch_bounds__(256) void fit_center_finalize_kernel(FitDev dv, F32Dev fd, float* __restrict__ w_out) {
+  __shared__ double red[256];
+  __shared__ double b[16];
+  const int t = threadIdx.x, FP = dv.FP, K = dv.K, KF = dv.K * dv.FP;
+  for (int k = 0; k < K; ++k) {
+    double a = 0.0;  // over the fp32 coefficients as exported: their rounding is compensated, not doubled
+    for (int f = t; f < dv.F; f += 256) a += (double)fd.center[f] * (double)w_out[k * FP + f];
+    a = center_block_sum(a, red);
+    if (t == 0) b[k] = (double)dv.x[KF + k] - a;
+  }
+  if (t == 0) {
+    double bm = 0.0;
+    for (int k = 0; k < K; ++k) bm += b[k];
+    bm /= (double)K;
+    for (int k = 0; k < K; ++k) w_out[KF + k] = (float)(b[k] - bm);
+  }
+}
+
+__global__ __launch_bounds__(256) void fit_center_grad_kernel(FitDev dv, F32Dev fd, float* __restrict__ grad) {
+  const int e = blockIdx.x * 256 + threadIdx.x, FP = dv.FP, KF = dv.K * dv.FP;
+  if (e >= dv.n) return;
+  float g = dv.g_t[e];
+  if (e < KF) {
+    const int k = e / FP, f = e - k * FP;
+    g = (float)((double)g + (double)fd.center[f] * (double)dv.g_t[KF + k]);
+  }
+  grad[e] = g;
 }
 
 // ---------------------------------------------------------------------------
 // Rows < N only are written; a row's outputs come from its own MFMA rows and its own 8
 // threads, so they do not depend on the rows beside it.
-template <int FP>
+template <int FP, bool kCenter = false>
 __global__ __launch_bounds__(256) void score_f32_kernel(FitDev dv, F32Dev fd, ScoreOut o) {
   extern __shared__ __attribute__((aligned(16))) char lds[];
   const F32Lds<FP> L(lds);
@@ -284,11 +433,12 @@ __global__ __launch_bounds__(256) void score_f32_kernel(FitDev dv, F32Dev fd, Sc
   if (tid == 0) noor = 0;  // (published by the barriers of the first tile)
   WFrag<FP> wf;
   load_wfrag<FP>(wf, dv.whi, dv.wlo, K);
+  const Center<FP, kCenter> cen(fd.center);
   const float bz0 = dv.b_eff[sc0], bz1 = dv.b_eff[sc0 + 1];
   const int ntiles = (N + 31) >> 5;  // <= Npad / 32: every staged row is readable
   for (int tile = blockIdx.x; tile < ntiles; tile += gridDim.x) {
     const int64_t row0 = (int64_t)tile * 32, row = row0 + sr;
-    stage_and_forward<FP>(L, fd.X, dv.y, row0, wf);
+    stage_and_forward<FP, kCenter>(L, fd.X, dv.y, row0, wf, cen);
     const int yl = L.ylab[sr];
     const float z0 = load_logit(L.red, sr, sc0) + bz0, z1 = load_logit(L.red, sr, sc0 + 1) + bz1;
     float bv = v0 && z0 == z0 ? z0 : -INFINITY;
@@ -345,6 +495,8 @@ void prepare_fit_f32_kernels() {
   for_each_int<128, 256, 512, 1024>([&](auto fp) {
     (void)hipFuncSetAttribute((const void*)fit_lossgrad_f32_kernel<fp()>, kDyn, (int)fit_f32_lds_bytes(fp()));
     (void)hipFuncSetAttribute((const void*)score_f32_kernel<fp()>, kDyn, (int)fit_f32_lds_bytes(fp()));
+    (void)hipFuncSetAttribute((const void*)fit_lossgrad_f32_kernel<fp(), true>, kDyn, (int)fit_f32_lds_bytes(fp()));
+    (void)hipFuncSetAttribute((const void*)score_f32_kernel<fp(), true>, kDyn, (int)fit_f32_lds_bytes(fp()));
   });
   done = true;
 }
@@ -354,16 +506,34 @@ void launch_fit_stats_f32(const FitDev& dv, const F32Dev& fd, int G, hipStream_t
   fit_stats_f32_fin_kernel<<<(dv.FP + 255) / 256, 256, 0, s>>>(dv, fd, G);
 }
 
-void launch_fit_lossgrad_f32(const FitDev& dv, const F32Dev& fd, int G, hipStream_t s) {
+void launch_fit_lossgrad_f32(const FitDev& dv, const F32Dev& fd, int G, bool centred, hipStream_t s) {
   dispatch_f32_fp(dv.FP, [&](auto fp) {
-    fit_lossgrad_f32_kernel<fp()><<<G, 256, fit_f32_lds_bytes(fp()), s>>>(dv, fd);
+    if (centred)
+      fit_lossgrad_f32_kernel<fp(), true><<<G, 256, fit_f32_lds_bytes(fp()), s>>>(dv, fd);
+    else
+      fit_lossgrad_f32_kernel<fp()><<<G, 256, fit_f32_lds_bytes(fp()), s>>>(dv, fd);
   });
 }
 
-void launch_score_f32(const FitDev& dv, const F32Dev& fd, int G, const ScoreOut& o, hipStream_t s) {
+void launch_score_f32(const FitDev& dv, const F32Dev& fd, int G, bool centred, const ScoreOut& o, hipStream_t s) {
   dispatch_f32_fp(dv.FP, [&](auto fp) {
-    score_f32_kernel<fp()><<<G, 256, fit_f32_lds_bytes(fp()), s>>>(dv, fd, o);
+    if (centred)
+      score_f32_kernel<fp(), true><<<G, 256, fit_f32_lds_bytes(fp()), s>>>(dv, fd, o);
+    else
+      score_f32_kernel<fp()><<<G, 256, fit_f32_lds_bytes(fp()), s>>>(dv, fd, o);
   });
+}
+
+void launch_fit_center_begin(const FitDev& dv, const F32Dev& fd, const float* w0, int raw, hipStream_t s) {
+  fit_center_begin_kernel<<<1, 256, 0, s>>>(dv, fd, w0, raw);
+}
+
+void launch_fit_center_finalize(const FitDev& dv, const F32Dev& fd, float* w_out, hipStream_t s) {
+  fit_center_finalize_kernel<<<1, 256, 0, s>>>(dv, fd, w_out);
+}
+
+void launch_fit_center_grad(const FitDev& dv, const F32Dev& fd, float* grad, hipStream_t s) {
+  fit_center_grad_kernel<<<(dv.n + 255) / 256, 256, 0, s>>>(dv, fd, grad);
 }
 
 }  // namespace psx

@@ -16,7 +16,11 @@ class F32BatchFitter : public FitDriver {
  public:
   // max_wg: workgroups of one launch.  max_wg <= 0: as many per compute unit as the two
   // tile images leave room for in its LDS (fit_f32_wg_per_cu: 1 at 1,024 .. 4 at 128).
-  F32BatchFitter(int K, int F, int FP, int hist, int max_wg);
+  // centred: every kernel multiplies x - c_f, c the columns' means (the statistics pass writes
+  // them, or set_center); the optimiser runs in (beta, b' = b + sum_f c_f w_f), and what goes
+  // in and comes out -- w0, the fitted weights, loss_grad's gradient, score's weights -- stays
+  // in raw coordinates.  Off: exactly the uncentred launches.
+  F32BatchFitter(int K, int F, int FP, int hist, int max_wg, bool centred = false);
   ~F32BatchFitter() override;
 
   // X [Npad][FP] fp32 with Npad = N rounded up to 32 (padding rows and columns zero),
@@ -24,6 +28,13 @@ class F32BatchFitter : public FitDriver {
   // statistics (a fit needs them; loss_grad and score do not).
   void set_data(const float* X, const int32_t* y, int64_t N, int64_t Npad, bool stats, hipStream_t s);
   void read_std(float* std_out, hipStream_t s);  // [FP]
+  // The centre of a dataset loaded without statistics (a scorer's: the training set's), c [FP]
+  // on the device with zeros in the padding; copied.  set_data forgets it.
+  void set_center(const float* c, hipStream_t s);
+  void read_center(float* c_out, hipStream_t s);  // [FP]
+  bool centred() const { return centred_; }
+  // loss_grad with the gradient left in centred coordinates, with respect to (w, b').
+  double loss_grad_centred(const float* w, float* grad, hipStream_t s);
   // Score the resident rows with the weights w ([K*FP + K], the model's device layout):
   // o's row outputs are [N]; labels are required, o.hist must be null.  Ends a fit in
   // progress (its trial point is overwritten).
@@ -44,7 +55,11 @@ class F32BatchFitter : public FitDriver {
  private:
   FitDev dv_{};  // (its bf16 row pointer stays null)
   F32Dev fd_{};
+  void need_center(const char* what) const;
   bool have_stats_ = false;
+  const bool centred_;
+  bool have_center_ = false;
+  bool export_raw_ = true;  // export_grad maps a centred gradient back (off inside loss_grad_centred)
   void* ws_ = nullptr;
   void* data_ws_ = nullptr;  // per-dataset partials (sized by the grid)
 };

@@ -2,13 +2,14 @@
 
 #include <climits>
 #include <stdexcept>
+#include <string>
 
 #include "solver.h"
 
 namespace psx {
 
-F32BatchFitter::F32BatchFitter(int K, int F, int FP, int hist, int max_wg)
-    : FitDriver(max_wg, fit_f32_wg_per_cu(fit_f32_fp_supported(FP) ? FP : kFitF32MaxFP)) {
+F32BatchFitter::F32BatchFitter(int K, int F, int FP, int hist, int max_wg, bool centred)
+    : FitDriver(max_wg, fit_f32_wg_per_cu(fit_f32_fp_supported(FP) ? FP : kFitF32MaxFP)), centred_(centred) {
   if (!fit_f32_fp_supported(FP))
     throw std::invalid_argument("fp32 rows: padded width " + std::to_string(FP) +
                                 " is not 128, 256, 512 or 1024 (two tile images of wider rows do not fit the LDS)");
@@ -25,6 +26,7 @@ F32BatchFitter::F32BatchFitter(int K, int F, int FP, int hist, int max_wg)
     carve_fit_vectors(c, dv_, fit_reduce_grid(dv_.n));
     c.take(dv_.std_, FP), c.take(dv_.inv_std, FP), c.take(dv_.b_eff, 16);
     c.take(dv_.whi, (size_t)16 * FP), c.take(dv_.wlo, (size_t)16 * FP);
+    c.take(fd_.center, FP);
   };
   Carver size;
   layout(size);
@@ -66,7 +68,7 @@ void F32BatchFitter::set_data(const float* X, const int32_t* y, int64_t N, int64
   hip_check(hipMalloc(&data_ws_, size.off), "hipMalloc(fp32 fit partials)");
   Carver place{static_cast<char*>(data_ws_)};
   layout(place);
-  have_stats_ = stats;
+  have_stats_ = have_center_ = stats;
   if (stats) {
     launch_fit_stats_f32(dv_, fd_, G_, s);
     hip_check(hipGetLastError(), "fit_stats_f32 launch");
@@ -77,22 +79,54 @@ void F32BatchFitter::score(const float* w, const ScoreOut& o, hipStream_t s) {
   if (!fd_.X) throw std::runtime_error("score: no dataset (set_data first)");
   if (!w || !o.pred || !o.conf || !o.oor) throw std::invalid_argument("score: null weights or output buffers");
   if (o.hist) throw std::invalid_argument("score: the fp32-row scorer has no score histogram");
+  need_center("score");
   end_fit();
-  launch_fit_begin(dv_, w, 1, /*raw=*/1, s);  // the weights' fragments and intercepts
-  launch_score_f32(dv_, fd_, G_, o, s);
+  launch_begin(w, 1, /*raw=*/1, s);  // the weights' fragments and intercepts
+  launch_score_f32(dv_, fd_, G_, centred_, o, s);
   hip_check(hipGetLastError(), "score_f32 launch");
+}
+
+void F32BatchFitter::need_center(const char* what) const {
+  if (centred_ && !have_center_)
+    throw std::runtime_error(std::string(what) + ": the centred mode needs the dataset's statistics or set_center");
+}
+
+void F32BatchFitter::set_center(const float* c, hipStream_t s) {
+  if (!fd_.X) throw std::runtime_error("set_center: no dataset (set_data first)");
+  if (!c) throw std::invalid_argument("set_center: null centre");
+  end_fit();
+  hip_check(hipMemcpyAsync(fd_.center, c, (size_t)dv_.FP * 4, hipMemcpyDeviceToDevice, s), "hipMemcpyAsync(centre)");
+  hip_check(hipStreamSynchronize(s), "hipStreamSynchronize(centre)");  // the caller's buffer may go
+  have_center_ = true;
+}
+
+void F32BatchFitter::read_center(float* c_out, hipStream_t s) {
+  if (!have_center_) throw std::runtime_error("read_center: no statistics and no set_center");
+  hip_check(hipMemcpyAsync(c_out, fd_.center, (size_t)dv_.FP * 4, hipMemcpyDeviceToDevice, s), "hipMemcpyAsync(centre)");
+  hip_check(hipStreamSynchronize(s), "hipStreamSynchronize(centre)");
+}
+
+double F32BatchFitter::loss_grad_centred(const float* w, float* grad, hipStream_t s) {
+  if (!centred_) throw std::runtime_error("loss_grad_centred: the fitter was built without the centred mode");
+  struct Restore {
+    bool& v;
+    ~Restore() { v = true; }
+  } restore{export_raw_};
+  export_raw_ = false;
+  return loss_grad(w, grad, s);
 }
 
 std::vector<float> F32BatchFitter::time_launches(const float* w, int reps, hipStream_t s) {
   if (!fd_.X || !w || reps < 1) throw std::invalid_argument("time_launches: a dataset, weights and reps >= 1");
+  need_center("time_launches");
   end_fit();
-  launch_fit_begin(dv_, w, 1, /*raw=*/1, s);
+  launch_begin(w, 1, /*raw=*/1, s);
   hipEvent_t ev[3];
   for (auto& e : ev) hip_check(hipEventCreate(&e), "hipEventCreate");
   std::vector<float> ms(2, 0.f);
   for (int r = 0; r < reps; ++r) {
     hip_check(hipEventRecord(ev[0], s), "hipEventRecord");
-    launch_fit_lossgrad_f32(dv_, fd_, G_, s);
+    launch_fit_lossgrad_f32(dv_, fd_, G_, centred_, s);
     hip_check(hipEventRecord(ev[1], s), "hipEventRecord");
     launch_fit_reduce(dv_, G_, 0.0, /*raw=*/1, s);
     hip_check(hipEventRecord(ev[2], s), "hipEventRecord");
@@ -113,11 +147,13 @@ FitVectors F32BatchFitter::vectors() const {
 
 void F32BatchFitter::launch_begin(const float* w0, int zero_const, int raw, hipStream_t s) {
   if (!raw && !have_stats_) throw std::runtime_error("fit: the dataset was loaded without statistics");
+  need_center("evaluation");
   launch_fit_begin(dv_, w0, zero_const, raw, s);
+  if (centred_) launch_fit_center_begin(dv_, fd_, w0, raw, s);  // the intercepts become b'
 }
 
 void F32BatchFitter::launch_eval(double reg, int raw, hipStream_t s) {
-  launch_fit_lossgrad_f32(dv_, fd_, G_, s);
+  launch_fit_lossgrad_f32(dv_, fd_, G_, centred_, s);
   launch_fit_reduce(dv_, G_, reg, raw, s);
 }
 
@@ -125,9 +161,11 @@ void F32BatchFitter::launch_update(const FitStep& st, hipStream_t s) { launch_fi
 
 void F32BatchFitter::launch_finalize(int center, float* w_out, hipStream_t s) {
   launch_fit_finalize(dv_, center, w_out, s);
+  if (centred_) launch_fit_center_finalize(dv_, fd_, w_out, s);  // b' -> the raw intercepts
 }
 
 void F32BatchFitter::export_grad(float* grad, hipStream_t s) {
+  if (centred_ && export_raw_) return launch_fit_center_grad(dv_, fd_, grad, s);
   hip_check(hipMemcpyAsync(grad, dv_.g_t, (size_t)dv_.n * 4, hipMemcpyDeviceToDevice, s), "hipMemcpyAsync(gradient)");
 }
 

@@ -94,6 +94,7 @@ class FitResult:
     # training set touches and ``std`` their [U] sigmas (every other feature is excluded: sigma 0, coefficient 0)
     features: torch.Tensor | None = None
     holdout_log_loss: float | None = None  # weighted mean loss of the held-out fold at ``w`` (FitWeights.holdout)
+    center: torch.Tensor | None = None  # [F] fp32 centre of a centred fp32-row fit (psx/ops/fit_f32.py); ``w`` is raw
 
     def save(self, path_dir: str) -> str:
         """Write ``server.ckpt`` into ``path_dir`` (for ``Scorer.from_checkpoint`` /

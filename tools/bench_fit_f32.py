@@ -1,7 +1,9 @@
 """fp32-row fit (csrc/kernels/fit_f32.hip) on one GPU beside the bf16 fit on the same rows rounded:
 one evaluation (``loss_grad``), its launches, and one scoring pass of each.
 
-    python tools/bench_fit_f32.py [--rows 1048576] [--features 1024] [--classes 6] [--out FILE]
+    python tools/bench_fit_f32.py [--rows 1048576] [--features 1024] [--classes 6] [--center] [--out FILE]
+
+``--center`` times the centred mode of the fp32 family (``F32Fitter(center=True)``, the scorer with the rows' centre).
 
 The two families are timed alternately in one session (medians of ``--repeats`` after warm-up calls,
 device events around the whole call, host side included); bytes/s count one read of the rows,
@@ -50,6 +52,7 @@ def main(argv=None):
     ap.add_argument("--classes", type=int, default=6)
     ap.add_argument("--repeats", type=int, default=11)
     ap.add_argument("--warmup", type=int, default=3)
+    ap.add_argument("--center", action="store_true", help="the fp32 family's centred mode")
     ap.add_argument("--out", default=None, help="also write the results as JSON")
     a = ap.parse_args(argv)
     if not torch.cuda.is_available():
@@ -64,22 +67,23 @@ def main(argv=None):
     y = torch.randint(0, K, (rows,), generator=g, device=dev).to(torch.int32)
     ds32, ds16 = Dataset(X, y, spec.F), Dataset(X.to(torch.bfloat16), y, spec.F)
     w = spec.init("random", seed=1, scale=0.05).to(dev)
-    f32, f16 = F32Fitter(spec, dev), BatchFitter(spec, dev)
+    f32, f16 = F32Fitter(spec, dev, center=a.center), BatchFitter(spec, dev)
     f32.loss_grad(ds32, w)
     f16.loss_grad(ds16, w)
-    s32, s16 = F32Scorer(spec, ds32, dev), Scorer(spec, w, dev)
+    center = f32.loss_grad_centred(ds32, w)[2][: spec.F] if a.center else None
+    s32, s16 = F32Scorer(spec, ds32, dev, center=center), Scorer(spec, w, dev)
     b32, b16 = rows * spec.Fp * 4, rows * spec.Fp * 2
     ev32, ev16, sc32, sc16 = alternated(
         [lambda: f32.loss_grad(ds32, w), lambda: f16.loss_grad(ds16, w), lambda: s32.score(w), lambda: s16.score(ds16)],
         a.repeats, a.warmup)
     lm = f32._native.time_launches(w.data_ptr(), 5, stream_handle(dev))
-    out = {"rows": rows, "F": spec.F, "Fp": spec.Fp, "K": K, "grid_f32": int(f32._native.grid),
+    out = {"rows": rows, "F": spec.F, "Fp": spec.Fp, "K": K, "center": bool(a.center), "grid_f32": int(f32._native.grid),
            "grid_bf16": int(f16._native.grid), "eval_ms": {"fp32": ev32, "bf16": ev16},
            "score_ms": {"fp32": sc32, "bf16": sc16}, "launch_ms_fp32": {"lossgrad": lm[0], "reduce": lm[1]},
            "eval_TBps": {"fp32": b32 / ev32 / 1e9, "bf16": b16 / ev16 / 1e9},
            "score_TBps": {"fp32": b32 / sc32 / 1e9, "bf16": b16 / sc16 / 1e9},
            "lossgrad_launch_TBps_fp32": b32 / lm[0] / 1e9}
-    print(f"rows {rows} x {spec.Fp} (F {spec.F}), K {K}: fp32 {b32 / 1e9:.2f} GB (grid {out['grid_f32']}), "
+    print(f"rows {rows} x {spec.Fp} (F {spec.F}), K {K}{', centred' if a.center else ''}: fp32 {b32 / 1e9:.2f} GB (grid {out['grid_f32']}), "
           f"bf16 {b16 / 1e9:.2f} GB (grid {out['grid_bf16']})")
     for name, ms, tb in (("evaluation", out["eval_ms"], out["eval_TBps"]), ("score pass", out["score_ms"], out["score_TBps"])):
         print(f"{name:11s} fp32 {ms['fp32']:8.3f} ms {tb['fp32']:.3f} TB/s | bf16 {ms['bf16']:8.3f} ms {tb['bf16']:.3f} TB/s"
